@@ -22,7 +22,7 @@ measurement of that regime (`also_measured.config3_B4`: 1 + 3 steps at 4 views o
 
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
 N > 1 runs one rank per GPU over RCCL -- under torch.distributed.run (RANK / WORLD_SIZE in the environment), or spawned by
-bench.py itself when it is started plainly (it re-execs under torch.distributed.run): every rank distils its own novel
+bench.py itself when it is started plainly (it runs torch.distributed.run as a child process): every rank distils its own novel
 view (weak scaling: the headline); the ranks all-gather the rendered latents and all-reduce (mean) the NGP gradients
 before each optimiser step so the replicas stay identical; that they are is checked once, after the timed region.
 Every line (N = 1 included) also carries `also_measured.config3_total32`: BASELINE configs[3] as the strong-scaling experiment it
@@ -212,6 +212,7 @@ class HotPath:
         from sparsefusion_amd.utils.losses import fusion_loss, render_loss, upsample2x
         img, sil = self.render(self.rays_in)
         loss = render_loss(img, sil, self.target_rgb, self.target_mask, 1.0, 1.0, 1e-3, 1e-3)      # distillation.py:217-241, one launch each way
+        loss_input = loss.detach()
         self.grads.zero()
         loss.backward()
         self.sync_grads()
@@ -244,6 +245,36 @@ class HotPath:
         loss.backward()
         self.sync_grads()
         self.optim.step()
+        # what a caller of the step receives (references only: no copy, no sync); the NGP parameters are read from self.ngp
+        self.last_outputs = {"loss_input_view": loss_input, "loss_novel_view": loss.detach(), "novel_rgb": img.detach(),
+                             "novel_silhouette": sil.detach(), "latents": latents, "pred_x0": pred_x0, "pred_img": pred_img,
+                             "alpha_cumprod": acp}
+
+
+DUMP_MAX_BYTES = 64 << 20         # --dump-outputs: all arrays together
+DUMP_MAX_ELEMS = 1 << 21          # per array; a larger one is written as a fixed seeded sample of this many elements
+
+
+def dump_outputs(hp, out_dir):
+    """Writes the last step's outputs and the NGP parameters after its optimiser step as <out_dir>/<name>.npy (float32).  An
+    array of more than DUMP_MAX_ELEMS elements is written flattened, as the elements at a fixed sorted random index set
+    (numpy seed 0, the same on every run); returns {name: {"shape": full shape, "sampled": bool}}."""
+    arrays = dict(hp.last_outputs)
+    arrays.update({"ngp." + k: p.detach() for k, p in hp.ngp.named_parameters()})
+    os.makedirs(out_dir, exist_ok=True)
+    index, total = {}, 0
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        entry = {"shape": list(a.shape), "sampled": a.size > DUMP_MAX_ELEMS}
+        if entry["sampled"]:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit("--dump-outputs: the arrays exceed %d bytes" % DUMP_MAX_BYTES)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+        index[name] = entry
+    return index
 
 
 def time_region(fn, iters):
@@ -401,13 +432,22 @@ def lds_conv_roofline(hp):
     return out
 
 
+def cpu_threads():
+    """The threads this process may use: OMP_NUM_THREADS when it names a count (its first field: "16,4" -> 16), else the CPUs in the
+    process's affinity mask -- never the machine's whole CPU count."""
+    first = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    if first.isdigit() and int(first) > 0:
+        return int(first)
+    return max(1, len(os.sched_getaffinity(0)))
+
+
 def cpu_baseline(max_thres):
     """The CPU oracle (a port: the reference has no CPU path for its CUDA kernels) timed on this host, on a
     bounded sample of the same workload, scaled to one step."""
     from oracle import lpips_ref, ngp_ref, unet_ref, vae_ref
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     from unet_common import spec
-    cores = min(32, os.cpu_count() or 1)          # torch CPU kernels stop scaling (and oversubscribe) beyond ~32 threads
+    cores = min(32, cpu_threads())                 # torch CPU kernels stop scaling (and oversubscribe) beyond ~32 threads
     torch.set_num_threads(cores)
     os.environ["OMP_NUM_THREADS"] = str(cores)
     p = ngp_ref.init_params(bound=4, seed=1, table_std=0.5, sigma_bias=-3.0)
@@ -468,7 +508,12 @@ def main():
     ap.add_argument("--no-also-measured", action="store_true", help="skip the short configs[3] (B = 4) measurement the default line carries")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 counter pass (child process) that fills roofline.traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, novel-view render, latents, PLMS x0 "
+                         "prediction, decoded image, alpha_cumprod, NGP parameters after the optimiser step) as DIR/<name>.npy, float32, rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == 3 and args.views_per_gpu == 1:
         args.views_per_gpu = 4
     if args.config == 4:
@@ -482,14 +527,15 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` spawns its own ranks, as the reference's demo does (demo.py:180 mp.spawn(fit, nprocs=gpus),
-        # :22 init_process_group): re-exec under torch.distributed.run on this node, one rank per GPU, rendezvous on 127.0.0.1
+        # :22 init_process_group): run torch.distributed.run as a child process on this node, one rank per GPU, rendezvous on 127.0.0.1
         # (the container hostname may not resolve).  Under torchrun (WORLD_SIZE set) this branch is never taken.
         import socket
         with socket.socket() as s:
             s.bind(("127.0.0.1", 0))
             port = s.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     if args.gpus > 1 and args.gpus != world:
         raise SystemExit("--gpus %d does not match WORLD_SIZE=%d of the launcher" % (args.gpus, world))
     backend = os.environ.get("SF_BENCH_BACKEND", "nccl")         # "gloo": dry-run of the multi-rank path on fewer GPUs than ranks
@@ -535,6 +581,7 @@ def main():
     if multi_rank:
         torch.distributed.all_reduce(dt, op=torch.distributed.ReduceOp.MAX)
     ms_per_step = float(dt) / args.steps * 1e3
+    dumped = dump_outputs(hp, args.dump_outputs) if args.dump_outputs and rank == 0 else None      # before any untimed step below
     hp.verify_replicas()                                            # once, OUTSIDE the timed region
     total32 = None
     if args.config == 1 and args.views_per_gpu == 1 and not strong and not args.no_also_measured and 32 % world == 0:
@@ -692,6 +739,8 @@ def main():
             res["multi_gpu"] = multi
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.max_thres)
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "step": "last timed step", "arrays": dumped}
         print(json.dumps(res))
     if multi_rank:
         torch.distributed.destroy_process_group()

@@ -158,7 +158,9 @@ typedef struct {
   float bound;               /* scene bound (inputs mapped (x+b)/(2b))      */
 } sf_ngp_field;
 
-/* Gradient outputs of the field (all caller-zeroed, accumulated with atomics) */
+/* Gradient outputs of the field (caller-zeroed; the backward adds its gradients into them).  Contributions below a size
+ * bound are summed in 64-bit fixed point first, so their total does not depend on the order of the adds; larger or
+ * non-finite ones are added with fp32 atomics (see csrc/sf_dev.h). */
 typedef struct {
   float* g_embeddings;
   float* g_w0; float* g_b0;

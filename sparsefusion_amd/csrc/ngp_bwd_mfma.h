@@ -34,7 +34,9 @@
 struct FBArgs {
   const float* table; const float* w0; const float* b0; const float* w1; const float* b1; const float* w2; const float* b2;
   float bound;
-  float* g_w0; float* g_b0; float* g_w1; float* g_b1; float* g_w2; float* g_b2;
+  long long* g_w0; long long* g_b0; long long* g_w1; long long* g_b1; long long* g_w2; long long* g_b2;   // fixed-point sums (sf_dev.h)
+  float* f_w0; float* f_b0; float* f_w1; float* f_b1; float* f_w2; float* f_b2;   // the fp32 gradients (addends >= thr, sf_grad_add)
+  float thr;
   NgpLevels lv;
   const float* rays_o; const float* rays_d; const float* aabb; const float* z_s; const float* dsig; const float* drgb;
   float* dfeat_out;          // level-major [L][dfeat_P][2] or null (table frozen)
@@ -354,20 +356,20 @@ SF_KERNEL(256) void k_ngp_field_bwd_mfma(FBArgs a) {
     sf_wave_sync();                                      // before the next trip restages F / H1 / H2 / DO / INS
   }
 
-  // ---- flush this wave's gradient tiles (row j = jt*16 + 4*kq + r, column li: 16 lanes = one 64-byte line per atomic request)
+  // ---- flush this wave's gradient tiles (row j = jt*16 + 4*kq + r, column li) as fixed-point integer adds: order-independent sums
 #pragma unroll
   for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int j = jt * 16 + 4 * kq + r;
 #pragma unroll
-      for (int kt = 0; kt < 4; ++kt) sf_global_add(a.g_w1 + j * NGP_HID + kt * 16 + li, acc1[jt][kt][r]);
-      sf_global_add(a.g_w0 + j * NGP_FEAT + li, acc0[jt][0][r]);
-      sf_global_add(a.g_w0 + j * NGP_FEAT + 16 + li, acc0[jt][1][r]);
+      for (int kt = 0; kt < 4; ++kt) sf_grad_add(a.g_w1 + j * NGP_HID + kt * 16 + li, a.f_w1 + j * NGP_HID + kt * 16 + li, acc1[jt][kt][r], a.thr);
+      sf_grad_add(a.g_w0 + j * NGP_FEAT + li, a.f_w0 + j * NGP_FEAT + li, acc0[jt][0][r], a.thr);
+      sf_grad_add(a.g_w0 + j * NGP_FEAT + 16 + li, a.f_w0 + j * NGP_FEAT + 16 + li, acc0[jt][1][r], a.thr);
     }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) sf_global_add(a.g_w2 + kq * NGP_HID + 4 * li + i, acc2[i]);
-  if (li == 0) sf_global_add(a.g_b2 + kq, accb2);
-  sf_global_add(a.g_b1 + lane, accb1);
-  sf_global_add(a.g_b0 + lane, accb0);
+  for (int i = 0; i < 4; ++i) sf_grad_add(a.g_w2 + kq * NGP_HID + 4 * li + i, a.f_w2 + kq * NGP_HID + 4 * li + i, acc2[i], a.thr);
+  if (li == 0) sf_grad_add(a.g_b2 + kq, a.f_b2 + kq, accb2, a.thr);
+  sf_grad_add(a.g_b1 + lane, a.f_b1 + lane, accb1, a.thr);
+  sf_grad_add(a.g_b0 + lane, a.f_b0 + lane, accb0, a.thr);
 }

@@ -111,18 +111,18 @@ __global__ __launch_bounds__(64) void k_ngp_sample_fine(
 #define SC_RAYS 64
 #define SC_SLOTS 4096
 #define SC_EMPTY 0xffffffffu
-// NT threads share one 80 KB LDS cache (r04: 4096 slots of doubles; r02: 8192 of floats) (one workgroup per CU): NT = 1024 puts 4 waves on every SIMD -- the loop body is a
+// NT threads share one 80 KB LDS cache (4096 slots of 64-bit fixed-point sums; r02: 8192 of floats) (one workgroup per CU): NT = 1024 puts 4 waves on every SIMD -- the loop body is a
 // chain of dependent global loads, hash arithmetic and LDS atomics, and with the first version's 256 threads (ONE wave per
 // SIMD) every one of those latencies was exposed.  `last_level`: levels [0, last_level) are walked by this kernel.
 template <int NT>
 __global__ __launch_bounds__(NT) void k_ngp_scatter(
-    NgpLevels lv, float bound, float* __restrict__ gtable, const float* __restrict__ rays_o,
+    NgpLevels lv, float bound, long long* __restrict__ gtable, float* __restrict__ gtable_f, float thr, const float* __restrict__ rays_o,
     const float* __restrict__ rays_d, const float* __restrict__ aabb, const float* __restrict__ z_s,
     const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t rays_per_row, uint32_t cached_levels,
     uint32_t last_level, uint32_t sc_run) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   uint32_t* tags = reinterpret_cast<uint32_t*>(smem);            // [SC_SLOTS]
-  double* vals = reinterpret_cast<double*>(smem + SC_SLOTS);     // [SC_SLOTS][2], doubles: ds_add_f64 is 7x the rate of ds_add_f32 (sf_dev.h)
+  long long* vals = reinterpret_cast<long long*>(smem + SC_SLOTS);   // [SC_SLOTS][2], fixed point (sf_dev.h): exact, order-independent sums
   const uint32_t P = N * T2;
   float box[6];
 #pragma unroll
@@ -135,10 +135,11 @@ __global__ __launch_bounds__(NT) void k_ngp_scatter(
   for (uint32_t l = 0; l < last_level; ++l) {
     const bool cached = l < cached_levels;
     if (cached) {
-      for (uint32_t s = threadIdx.x; s < SC_SLOTS; s += NT) { tags[s] = SC_EMPTY; vals[2 * s] = 0.0; vals[2 * s + 1] = 0.0; }
+      for (uint32_t s = threadIdx.x; s < SC_SLOTS; s += NT) { tags[s] = SC_EMPTY; vals[2 * s] = 0; vals[2 * s + 1] = 0; }
       __syncthreads();
     }
-    float* tab = gtable + (size_t)lv.offset[l] * 2;
+    long long* tab = gtable + (size_t)lv.offset[l] * 2;
+    float* ftab = gtable_f + (size_t)lv.offset[l] * 2;
     const uint32_t step = lv.resolution[l] + 1;
     const bool z_dropped = lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
     // lane quads share a sample: lane&1 = channel, lane&2 = x-corner.  The four adds of an x-corner pair (two
@@ -150,15 +151,19 @@ __global__ __launch_bounds__(NT) void k_ngp_scatter(
     // the same handful of LDS addresses, and same-address LDS atomics serialise (0.18 ms per level for ~1 us of work).
     const uint32_t runs = (T2 + sc_run - 1) / sc_run;
     auto flush = [&](uint32_t row, float v, uint32_t ch) {
+      if (!(fabsf(v) < thr)) {                                   // large / non-finite: the fp32 table (sf_grad_add)
+        sf_global_add(ftab + (size_t)row * 2 + ch, v);
+        return;
+      }
       if (cached) {
         const uint32_t slot = (row * 2654435761u) >> 20;         // 12 bits -> SC_SLOTS
         const uint32_t prev = atomicCAS(&tags[slot], SC_EMPTY, row);
         if (prev == SC_EMPTY || prev == row) {
-          sf_lds_add_f64(&vals[2 * slot + ch], (double)v);
+          sf_fix_add(&vals[2 * slot + ch], sf_fix_of(v));
           return;
         }
       }
-      SF_ATOMIC_ADD(tab + (size_t)row * 2 + ch, v);
+      sf_fix_add(tab + (size_t)row * 2 + ch, sf_fix_of(v));
     };
     for (uint32_t it = threadIdx.x; it < 4 * SC_RAYS * runs; it += NT) {
       const uint32_t q = it >> 2, ch = it & 1, xb = (it >> 1) & 1;
@@ -209,8 +214,8 @@ __global__ __launch_bounds__(NT) void k_ngp_scatter(
       for (uint32_t s = threadIdx.x; s < SC_SLOTS; s += NT) {
         const uint32_t row = tags[s];
         if (row != SC_EMPTY) {
-          SF_ATOMIC_ADD(tab + (size_t)row * 2, (float)vals[2 * s]);
-          SF_ATOMIC_ADD(tab + (size_t)row * 2 + 1, (float)vals[2 * s + 1]);
+          if (vals[2 * s]) sf_fix_add(tab + (size_t)row * 2, vals[2 * s]);
+          if (vals[2 * s + 1]) sf_fix_add(tab + (size_t)row * 2 + 1, vals[2 * s + 1]);
         }
       }
       __syncthreads();
@@ -222,7 +227,7 @@ __global__ __launch_bounds__(NT) void k_ngp_scatter(
 // latency of the loads in front of every atomic.  Work item = (level, sample) in level-major order (the dfeat layout),
 // lane quads as above: 16 contiguous bytes per atomic instruction and quad.
 __global__ __launch_bounds__(256) void k_ngp_scatter_fine(
-    NgpLevels lv, float bound, float* __restrict__ gtable, const float* __restrict__ rays_o,
+    NgpLevels lv, float bound, long long* __restrict__ gtable, float* __restrict__ gtable_f, float thr, const float* __restrict__ rays_o,
     const float* __restrict__ rays_d, const float* __restrict__ aabb, const float* __restrict__ z_s,
     const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t first_level, uint32_t P_stride, uint32_t p_off) {
   // this launch walks the N rays behind the (pre-offset) ray / sample pointers = points [p_off, p_off + N * T2) of a set of
@@ -246,7 +251,8 @@ __global__ __launch_bounds__(256) void k_ngp_scatter_fine(
     if (!ngp_unit(x, bound, x01)) continue;
     NgpCell c;
     ngp_cell(lv, l, x01, c);
-    float* tab = gtable + (size_t)lv.offset[l] * 2;
+    long long* tab = gtable + (size_t)lv.offset[l] * 2;
+    float* ftab = gtable_f + (size_t)lv.offset[l] * 2;
     const uint32_t step = lv.resolution[l] + 1;
     const bool z_dropped = lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
 #pragma unroll
@@ -257,7 +263,23 @@ __global__ __launch_bounds__(256) void k_ngp_scatter_fine(
       const float w1 = z_dropped ? SF_ADD(c.w[i1 & 3], c.w[(i1 & 3) + 4]) : c.w[i1];
       const float w = xb ? w1 : w0;
       const uint32_t row = xb ? c.row[i1] : c.row[i0];
-      SF_ATOMIC_ADD(tab + (size_t)row * 2 + ch, SF_MUL(w, dfc));
+      sf_grad_add(tab + (size_t)row * 2 + ch, ftab + (size_t)row * 2 + ch, SF_MUL(w, dfc), thr);
+    }
+  }
+}
+
+// Fixed-point gradient sums (sf_dev.h) -> the caller's fp32 gradients: dst[i] += acc[i] * 2^-44.  Segments are consecutive in acc.
+#define FIX_SEGS 7
+struct FixSegs { float* dst[FIX_SEGS]; uint64_t end[FIX_SEGS]; };
+__global__ __launch_bounds__(256) void k_fix_to_f32(const long long* __restrict__ acc, FixSegs sg) {
+  const uint64_t total = sg.end[FIX_SEGS - 1];
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
+    int k = 0;
+    while (i >= sg.end[k]) ++k;
+    const long long v = acc[i];
+    if (v != 0 && sg.dst[k]) {
+      const uint64_t j = i - (k ? sg.end[k - 1] : 0);
+      sg.dst[k][j] += (float)((double)v * SF_FIX_INV);
     }
   }
 }
@@ -417,8 +439,57 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   int dev_id = 0;                                  // raised dynamic-LDS limits are per-device function attributes
   if (hipGetDevice(&dev_id) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "hipGetDevice failed");
   float* dfeat = g->g_embeddings ? drgb + 3 * M : nullptr;        // NULL table gradient = table frozen
+  // every gradient is first summed in 64-bit fixed point (sf_dev.h: order-independent, so the result is the same on every run) in a
+  // stream-ordered scratch buffer: [table rows x 2 | w0 | b0 | w1 | b1 | w2 | b2], converted into the caller's buffers at the end
+  const uint64_t tab_n = dfeat ? (uint64_t)f->h_offsets[f->L] * 2 : 0;
+  FixSegs segs{};
+  {
+    float* dst[FIX_SEGS] = {g->g_embeddings, g->g_w0, g->g_b0, g->g_w1, g->g_b1, g->g_w2, g->g_b2};
+    const uint64_t len[FIX_SEGS] = {tab_n, NGP_HID * NGP_FEAT, NGP_HID, NGP_HID * NGP_HID, NGP_HID, NGP_OUT * NGP_HID, NGP_OUT};
+    uint64_t e = 0;
+    for (int k = 0; k < FIX_SEGS; ++k) { segs.dst[k] = dst[k]; e += len[k]; segs.end[k] = e; }
+  }
+  // the scratch comes from a memory pool this library owns (one per device, created once under a lock, kept mapped between calls so
+  // a call does not re-map it); the device's default pool and its settings are left alone
+  static std::mutex pool_mu;
+  static hipMemPool_t pools[32] = {};
+  hipMemPool_t pool = nullptr;
+  if (dev_id < 32) {
+    std::lock_guard<std::mutex> lk(pool_mu);
+    if (!pools[dev_id]) {
+      hipMemPoolProps props{};
+      props.allocType = hipMemAllocationTypePinned;
+      props.location.type = hipMemLocationTypeDevice;
+      props.location.id = dev_id;
+      hipMemPool_t np = nullptr;
+      uint64_t keep = UINT64_MAX;
+      if (hipMemPoolCreate(&np, &props) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot create the scratch pool");
+      if (hipMemPoolSetAttribute(np, hipMemPoolAttrReleaseThreshold, &keep) != hipSuccess) {
+        (void)hipMemPoolDestroy(np);
+        SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot configure the scratch pool");
+      }
+      pools[dev_id] = np;
+    }
+    pool = pools[dev_id];
+  }
+  struct FixBuf {
+    long long* p = nullptr; hipStream_t st = nullptr;
+    ~FixBuf() { if (p) (void)hipFreeAsync(p, st); }
+  } fix;
+  fix.st = st;
+  const uint64_t fix_bytes = segs.end[FIX_SEGS - 1] * sizeof(long long);
+  const hipError_t alloc = pool ? hipMallocFromPoolAsync(reinterpret_cast<void**>(&fix.p), fix_bytes, pool, st)
+                               : hipMallocAsync(reinterpret_cast<void**>(&fix.p), fix_bytes, st);
+  if (alloc != hipSuccess || !fix.p)
+    SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot allocate the gradient accumulators");
+  if (hipMemsetAsync(fix.p, 0, fix_bytes, st) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: memset failed");
+  long long* acc_tab = fix.p;
+  long long* acc_mlp = fix.p + tab_n;
+  // a fixed-point sum receives at most 8 addends per sample (the 8 corners of a cell, hash collisions included): thresholds per
+  // sf_dev.h keep every table sum below 2^18; larger addends take the fp32 atomics (sf_grad_add)
+  const float thr_tab = sf_fix_thr(8.0 * (double)M);
   const size_t lds2 = (size_t)FB_LDS_FLOATS * sizeof(float);
-  const size_t lds_sc = (size_t)SC_SLOTS * (sizeof(uint32_t) + 2 * sizeof(double));
+  const size_t lds_sc = (size_t)SC_SLOTS * (sizeof(uint32_t) + 2 * sizeof(long long));
   static unsigned attr_mask = 0;
   if (dev_id >= 32 || !(attr_mask & (1u << dev_id))) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
@@ -481,6 +552,7 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   NgpChunks plan = ngp_bwd_plan(N);                                            // (the entries buffer is sized for this chunking)
   if (!(dfeat && last < lv.L)) { plan.n = 1; plan.start[0] = 0; plan.start[1] = N; }
   const uint32_t n_chunks = plan.n;
+  const float thr_mlp = sf_fix_thr(4.0 * 256.0 * n_chunks);        // one addend per wave and launch: <= 256 workgroups x 4 waves per chunk
   // The side stream and its fork / join events are ONE set per device: two host threads (or two caller streams) rendering on the
   // same device would re-record each other's events, so the whole fork .. join section runs under the lock (host-side enqueue only:
   // microseconds).  The guard below joins the side stream into the caller's stream on EVERY exit path, error returns included.
@@ -507,7 +579,9 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
     // matrix-core field backward of chunk c: one wave per 32 points and trip, six fp32 GEMMs on v_mfma_f32_16x16x4_f32 (ngp_bwd_mfma.h)
     FBArgs a{};
     a.table = f->embeddings; a.w0 = f->w0; a.b0 = f->b0; a.w1 = f->w1; a.b1 = f->b1; a.w2 = f->w2; a.b2 = f->b2; a.bound = f->bound;
-    a.g_w0 = g->g_w0; a.g_b0 = g->g_b0; a.g_w1 = g->g_w1; a.g_b1 = g->g_b1; a.g_w2 = g->g_w2; a.g_b2 = g->g_b2;
+    a.g_w0 = acc_mlp + (segs.end[0] - tab_n); a.g_b0 = acc_mlp + (segs.end[1] - tab_n); a.g_w1 = acc_mlp + (segs.end[2] - tab_n);
+    a.g_b1 = acc_mlp + (segs.end[3] - tab_n); a.g_w2 = acc_mlp + (segs.end[4] - tab_n); a.g_b2 = acc_mlp + (segs.end[5] - tab_n);
+    a.f_w0 = g->g_w0; a.f_b0 = g->g_b0; a.f_w1 = g->g_w1; a.f_b1 = g->g_b1; a.f_w2 = g->g_w2; a.f_b2 = g->g_b2; a.thr = thr_mlp;
     a.lv = lv;
     a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3; a.aabb = aabb;
     a.z_s = z_sorted + (size_t)P0; a.dsig = dsig + (size_t)P0; a.drgb = drgb + (size_t)P0 * 3; a.dfeat_out = dfeat;
@@ -531,10 +605,10 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
       if (binned) {
         SBArgs b{};
         b.lv = lv; b.bound = f->bound; b.rays_o = a.rays_o; b.rays_d = a.rays_d; b.aabb = aabb; b.z_s = a.z_s; b.dfeat = dfeat;
-        b.gtable = g->g_embeddings; b.cursor = bin_cursor; b.ent = bin_ent;
+        b.gtable = acc_tab; b.gtable_f = g->g_embeddings; b.thr = thr_tab; b.cursor = bin_cursor; b.ent = bin_ent;
         b.P = Pc; b.T2 = T2; b.first_level = first_bin; b.P_stride = (uint32_t)M; b.p_off = P0; b.cap = bin_cap;
         SBRArgs r{};
-        r.lv = lv; r.gtable = g->g_embeddings; r.cursor = bin_cursor; r.ent = bin_ent; r.first_level = first_bin; r.cap = bin_cap;
+        r.lv = lv; r.gtable = acc_tab; r.gtable_f = g->g_embeddings; r.thr = thr_tab; r.cursor = bin_cursor; r.ent = bin_ent; r.first_level = first_bin; r.cap = bin_cap;
         for (uint32_t l = 0; l <= NGP_MAX_LEVELS; ++l) { b.bucket0[l] = bucket0[l]; r.bucket0[l] = bucket0[l]; }
         const uint32_t tiles = sf_div_up(Pc, SB_THREADS);
         k_ngp_bin<<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
@@ -544,7 +618,7 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
       } else {
         const uint64_t items = (uint64_t)4 * Pc * (lv.L - last);
         const uint32_t grid_f = (uint32_t)(items / 256 < 16384 ? (items + 255) / 256 : 16384);
-        k_ngp_scatter_fine<<<grid_f, 256, 0, sf>>>(lv, f->bound, g->g_embeddings, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, last,
+        k_ngp_scatter_fine<<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, last,
                                                    (uint32_t)M, P0);
         SF_CHECK_LAUNCH("ngp_scatter_fine");
       }
@@ -552,9 +626,15 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   }
   if (dfeat && last > 0) {
     const uint32_t grid_sc = sf_div_up(N, SC_RAYS);
-    k_ngp_scatter<1024><<<grid_sc, 1024, lds_sc, st>>>(lv, f->bound, g->g_embeddings, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, cached, last, sc_run);
+    k_ngp_scatter<1024><<<grid_sc, 1024, lds_sc, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, cached, last, sc_run);
     SF_CHECK_LAUNCH("ngp_scatter");
   }
   if (side_join.join()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: join failed");
-  return SF_OK;
+  {
+    const uint64_t total = segs.end[FIX_SEGS - 1];
+    const uint32_t grid_x = (uint32_t)(total / 256 < 4096 ? (total + 255) / 256 : 4096);
+    k_fix_to_f32<<<grid_x, 256, 0, st>>>(fix.p, segs);
+    SF_CHECK_LAUNCH("fix_to_f32");
+  }
+  return SF_OK;                                    // (fix frees the accumulators on the stream, behind the conversion)
 }

@@ -11,15 +11,15 @@
 //                     ONE returning device atomic on the bucket's cursor, and the 16-byte entries are stored there (plain stores:
 //                     the runs of a tile are assembled in its XCD's L2; the kernel is bound by the number of store instructions,
 //                     all of them divergent -- pairs halve it);
-//   k_ngp_bin_reduce  one workgroup per bucket: its entries stream in coalesced, accumulate in a 16 KB LDS slice of DOUBLES (ds_add_f64:
-//                     fp32 LDS atomics retire 0.33 lane-operations per clock and CU on gfx950, fp64 ones 2.3 -- sf_dev.h),
+//   k_ngp_bin_reduce  one workgroup per bucket: its entries stream in coalesced, accumulate in a 16 KB LDS slice of 64-bit fixed-point
+//                     integers (ds_add_u64: exact, so the sums do not depend on arrival order -- sf_dev.h),
 //                     and the slice is added to the gradient table with plain vector read-modify-writes -- the workgroup is the
 //                     only writer of those rows while it runs (stream order; the cached-level kernel owns other levels).
 // Device atomics per level: one per (tile, touched bucket), <= 64 per 4096 pairs, instead of one granule per pair.  A bucket that
 // overflows its capacity (a skewed `tiled` level, adversarial input) falls back to direct atomics for the overflow: always correct.
 // 16 KB of LDS each: both kernels run beside k_ngp_field_bwd_mfma's 113 KB on the same CU.
 // Reference semantics: external/gridencoder/src/gridencoder.cu:203-262 (kernel_grid_backward: atomicAdd per corner and channel);
-// values equal ngp_scatter (ngp_device.h) up to fp32 summation order, which atomics never fixed either.
+// values equal ngp_scatter (ngp_device.h) up to the one rounding of each contribution to fixed point (sf_dev.h).
 #pragma once
 #include "sf_dev.h"
 #include "ngp_device.h"
@@ -45,7 +45,9 @@ struct SBArgs {
   float bound;
   const float* rays_o; const float* rays_d; const float* aabb; const float* z_s;   // pre-offset to this launch's first ray
   const float* dfeat;          // level-major [L][P_stride][2], this launch's points at p_off
-  float* gtable;
+  long long* gtable;           // fixed-point table-gradient sums (sf_dev.h)
+  float* gtable_f;             // the fp32 table gradient (addends >= thr, sf_grad_add)
+  float thr;
   uint32_t* cursor;            // [buckets]: entries reserved so far (zero before the first k_ngp_bin of a reduce round)
   f32x4* ent;                  // [buckets][cap] 16-byte entries {word, a, b, ratio} (sb_pack below)
   uint32_t P, T2, first_level, P_stride, p_off, cap;
@@ -141,7 +143,8 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin(SBArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) c.w[i] = SF_ADD(c.w[i], c.w[i + 4]);
           }
-          float* tab = a.gtable + (size_t)a.lv.offset[l] * 2;
+          long long* tab = a.gtable + (size_t)a.lv.offset[l] * 2;
+          float* ftab = a.gtable_f + (size_t)a.lv.offset[l] * 2;
           const uint32_t b0 = a.bucket0[l];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -152,12 +155,12 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin(SBArgs a) {
               const bool full = pos >= a.cap;                            // bucket full: the pair goes straight to the table
               const bool split = (r1 >> SB_ROWS_LOG) != b;               // second row in another bucket (~1 pair in 1024): direct adds
               if (full || split) {
-                sf_global_add(tab + (size_t)r1 * 2, SF_MUL(w1, d[g][0]));
-                sf_global_add(tab + (size_t)r1 * 2 + 1, SF_MUL(w1, d[g][1]));
+                sf_grad_add(tab + (size_t)r1 * 2, ftab + (size_t)r1 * 2, SF_MUL(w1, d[g][0]), a.thr);
+                sf_grad_add(tab + (size_t)r1 * 2 + 1, ftab + (size_t)r1 * 2 + 1, SF_MUL(w1, d[g][1]), a.thr);
               }
               if (full) {
-                sf_global_add(tab + (size_t)r0 * 2, SF_MUL(w0, d[g][0]));
-                sf_global_add(tab + (size_t)r0 * 2 + 1, SF_MUL(w0, d[g][1]));
+                sf_grad_add(tab + (size_t)r0 * 2, ftab + (size_t)r0 * 2, SF_MUL(w0, d[g][0]), a.thr);
+                sf_grad_add(tab + (size_t)r0 * 2 + 1, ftab + (size_t)r0 * 2 + 1, SF_MUL(w0, d[g][1]), a.thr);
               } else {
                 a.ent[(size_t)(b0 + b) * a.cap + pos] = split ? sb_pack(r0, r0, w0, 0.0f, d[g][0], d[g][1]) : sb_pack(r0, r1, w0, w1, d[g][0], d[g][1]);
               }
@@ -172,7 +175,9 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin(SBArgs a) {
 
 struct SBRArgs {
   NgpLevels lv;
-  float* gtable;
+  long long* gtable;           // fixed-point table-gradient sums (sf_dev.h)
+  float* gtable_f;             // the fp32 table gradient (addends >= thr, sf_grad_add)
+  float thr;
   uint32_t* cursor; const f32x4* ent;
   uint32_t first_level, cap;
   uint32_t bucket0[NGP_MAX_LEVELS + 1];
@@ -184,7 +189,7 @@ struct SBRArgs {
 #define SBR_THREADS (SB_ROWS < 1024u ? (int)SB_ROWS : 1024)
 #define SBR_U 4
 SF_KERNEL(SBR_THREADS) void k_ngp_bin_reduce(SBRArgs a) {
-  SF_SHARED double acc[SB_ROWS * 2];
+  SF_SHARED long long acc[SB_ROWS * 2];                                 // fixed point (sf_dev.h): exact, order-independent sums
   const uint32_t gb = blockIdx.x, tid = threadIdx.x;
   uint32_t n = a.cursor[gb];
   if (n == 0) return;                                                    // (uniform: every thread read the same word)
@@ -192,6 +197,9 @@ SF_KERNEL(SBR_THREADS) void k_ngp_bin_reduce(SBRArgs a) {
   uint32_t l = a.first_level;
   while (l + 1 < a.lv.L && gb >= a.bucket0[l + 1]) ++l;
   const f32x4* ent = a.ent + (size_t)gb * a.cap;
+  float* ftab = a.gtable_f + ((size_t)a.lv.offset[l] + ((gb - a.bucket0[l]) << SB_ROWS_LOG)) * 2;   // this bucket's first row
+  // an addend below thr goes to the LDS slice in fixed point, any other straight to the fp32 table (sf_grad_add)
+  auto add = [&](uint32_t k, float v) { if (fabsf(v) < a.thr) sf_fix_add(&acc[k], sf_fix_of(v)); else sf_global_add(ftab + k, v); };
   f32x4 v[SBR_U];
   auto fetch = [&](uint32_t i0) {
 #pragma unroll
@@ -202,7 +210,7 @@ SF_KERNEL(SBR_THREADS) void k_ngp_bin_reduce(SBRArgs a) {
     }
   };
   fetch(0);                                                              // the first batch is in flight while the slice is zeroed
-  for (uint32_t k = tid; k < SB_ROWS * 2; k += SBR_THREADS) acc[k] = 0.0;
+  for (uint32_t k = tid; k < SB_ROWS * 2; k += SBR_THREADS) acc[k] = 0;
   sf_sync();
   if (tid == 0) a.cursor[gb] = 0;
   for (uint32_t i0 = 0; i0 < n; i0 += SBR_U * SBR_THREADS) {
@@ -216,11 +224,11 @@ SF_KERNEL(SBR_THREADS) void k_ngp_bin_reduce(SBRArgs a) {
         const uint32_t word = __builtin_bit_cast(uint32_t, vc[u][0]);
         const uint32_t q0 = word & (SB_ROWS - 1), q1 = q0 + ((word >> 20) & 2047u) - 1024u;      // both rows of the pair lie in this bucket
         const uint32_t qh = (word >> 31) ? q1 : q0, ql = (word >> 31) ? q0 : q1;
-        sf_lds_add_f64(&acc[2 * qh], (double)vc[u][1]);
-        sf_lds_add_f64(&acc[2 * qh + 1], (double)vc[u][2]);
+        add(2 * qh, vc[u][1]);
+        add(2 * qh + 1, vc[u][2]);
         if (vc[u][3] != 0.0f) {
-          sf_lds_add_f64(&acc[2 * ql], (double)(vc[u][1] * vc[u][3]));
-          sf_lds_add_f64(&acc[2 * ql + 1], (double)(vc[u][2] * vc[u][3]));
+          add(2 * ql, vc[u][1] * vc[u][3]);
+          add(2 * ql + 1, vc[u][2] * vc[u][3]);
         }
       }
     }
@@ -229,19 +237,20 @@ SF_KERNEL(SBR_THREADS) void k_ngp_bin_reduce(SBRArgs a) {
   const uint32_t row0 = (gb - a.bucket0[l]) << SB_ROWS_LOG;
   const uint32_t hs = a.lv.hsize[l];
   const uint32_t nrows = hs - row0 < SB_ROWS ? hs - row0 : SB_ROWS;
-  f32x2* tab = reinterpret_cast<f32x2*>(a.gtable + (size_t)a.lv.offset[l] * 2) + row0;
+  long long* tab = a.gtable + ((size_t)a.lv.offset[l] + row0) * 2;
   constexpr int RPT = SB_ROWS / SBR_THREADS;                             // rows per thread: all their loads first, then the stores
-  f32x2 t[RPT];
+  long long t[RPT][2];
 #pragma unroll
   for (int u = 0; u < RPT; ++u) {
     uint32_t q = u * SBR_THREADS + tid;
     if (q > nrows - 1) q = nrows - 1;
-    t[u] = tab[q];
+    t[u][0] = tab[2 * q];
+    t[u][1] = tab[2 * q + 1];
   }
 #pragma unroll
   for (int u = 0; u < RPT; ++u) {
     const uint32_t q = u * SBR_THREADS + tid;
-    const f32x2 s = {(float)acc[2 * q], (float)acc[2 * q + 1]};
-    if (q < nrows && (s[0] != 0.0f || s[1] != 0.0f)) tab[q] = f32x2{t[u][0] + s[0], t[u][1] + s[1]};
+    const long long s0 = acc[2 * q], s1 = acc[2 * q + 1];
+    if (q < nrows && (s0 != 0 || s1 != 0)) { tab[2 * q] = t[u][0] + s0; tab[2 * q + 1] = t[u][1] + s1; }
   }
 }

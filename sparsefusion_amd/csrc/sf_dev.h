@@ -11,6 +11,20 @@ typedef __attribute__((ext_vector_type(4))) sf_opnd bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
+// Reproducible gradient sums (the NGP backward): a contribution v with |v| < thr is rounded once to a signed 64-bit fixed-point
+// number in units of 2^-44 (5.7e-14) and summed with integer atomics, which are exact -- the total does not depend on the order in
+// which lanes, waves and workgroups arrive, as fp32 / fp64 atomics' does; one conversion to fp32 at the end.  Every other
+// contribution (|v| >= thr, Inf, NaN) is added to the fp32 gradient with an fp32 atomic as before, so it is never clipped or
+// wrapped and a non-finite gradient stays visible.  The caller picks thr <= 2^18 / (most addends one sum can receive), so no
+// fixed-point sum reaches 2^18 in magnitude: the int64 never overflows (sf_fix_thr).
+#define SF_FIX_ONE 17592186044416.0            // 2^44
+#define SF_FIX_INV (1.0 / SF_FIX_ONE)
+static inline float sf_fix_thr(double max_addends) {      // host: largest power of two <= 2^18 / max_addends
+  float t = 262144.0f;
+  while (t > 0x1p-40f && (double)t * max_addends > 262144.0) t *= 0.5f;
+  return t;
+}
+
 #ifdef SF_HOST_EMU
 #include "hip_emu.h"
 #define SF_KERNEL(...)
@@ -49,6 +63,12 @@ static inline void sf_lds_add_f64(double* p, double v) {
 static inline float sf_rsqrt(float v) { return 1.0f / sqrtf(v); }
 static inline void sf_wave_sync() { hipemu::t_wave->bar.wait(); }
 static inline void sf_global_add(float* p, float v) { sf_lds_add(p, v); }
+static inline long long sf_fix_of(float v) { return llrint((double)v * SF_FIX_ONE); }
+static inline void sf_fix_add(long long* p, long long v) { (void)__atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+static inline void sf_grad_add(long long* acc, float* f32, float v, float thr) {
+  if (fabsf(v) < thr) sf_fix_add(acc, sf_fix_of(v));
+  else sf_global_add(f32, v);
+}
 // v_mfma_f32_16x16x4_f32: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15], D[i = 4 * (lane >> 4) + r][j = lane & 15]
 static inline f32x4 sf_mfma4(float a, float b, f32x4 c) {
   hipemu::WaveState* w = hipemu::t_wave;
@@ -144,6 +164,14 @@ SF_DEV float sf_rsqrt(float v) { return rsqrtf(v); }
 SF_DEV void sf_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 typedef __attribute__((address_space(1))) float sf_dev_gfloat;
 SF_DEV void sf_global_add(float* p, float v) { (void)__builtin_amdgcn_global_atomic_fadd_f32((sf_dev_gfloat*)p, v); }
+SF_DEV long long sf_fix_of(float v) { return __double2ll_rn((double)v * SF_FIX_ONE); }
+// integer add (LDS: ds_add_u64, global: global_atomic_add_u64): exact, so the sum does not depend on the order of the adds
+SF_DEV void sf_fix_add(long long* p, long long v) { (void)atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v); }
+// fixed point when |v| < thr (false for NaN), else the fp32 atomic of the caller's gradient at the same index (see SF_FIX_ONE)
+SF_DEV void sf_grad_add(long long* acc, float* f32, float v, float thr) {
+  if (fabsf(v) < thr) sf_fix_add(acc, sf_fix_of(v));
+  else sf_global_add(f32, v);
+}
 SF_DEV f32x4 sf_mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 SF_DEV float sf_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
 SF_DEV long long sf_clock() { return (long long)wall_clock64(); }      // 100 MHz constant clock

@@ -50,13 +50,22 @@ extern "C" void emu_field_bwd(const float* table, const int32_t* h_offsets, uint
   }
   FBArgs a{};                                      // (feat_c / feat_f / perm stay null: the re-gather path)
   a.table = table; a.w0 = w0; a.b0 = b0; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.bound = bound;
-  a.g_w0 = g_w0; a.g_b0 = g_b0; a.g_w1 = g_w1; a.g_b1 = g_b1; a.g_w2 = g_w2; a.g_b2 = g_b2;
+  // the kernel sums its weight gradients in 64-bit fixed point (sf_dev.h); they are added to the float outputs as the product does
+  float* gout[6] = {g_w0, g_b0, g_w1, g_b1, g_w2, g_b2};
+  const int glen[6] = {NGP_HID * NGP_FEAT, NGP_HID, NGP_HID * NGP_HID, NGP_HID, NGP_OUT * NGP_HID, NGP_OUT};
+  std::vector<long long> gacc[6];
+  for (int k = 0; k < 6; ++k) gacc[k].assign(glen[k], 0);
+  a.g_w0 = gacc[0].data(); a.g_b0 = gacc[1].data(); a.g_w1 = gacc[2].data(); a.g_b1 = gacc[3].data(); a.g_w2 = gacc[4].data(); a.g_b2 = gacc[5].data();
+  a.f_w0 = g_w0; a.f_b0 = g_b0; a.f_w1 = g_w1; a.f_b1 = g_b1; a.f_w2 = g_w2; a.f_b2 = g_b2;
+  a.thr = sf_fix_thr(4.0 * grid);                  // one addend per wave, as the product's bound
   fill_levels(&a.lv, h_offsets, L, S, H, gridtype);
   a.rays_o = rays_o; a.rays_d = rays_d; a.aabb = aabb; a.z_s = z_s; a.dsig = dsig; a.drgb = drgb; a.dfeat_out = dfeat; a.dfeat_P = P; a.p_off = 0;
   a.P = P; a.T2 = T2;
   if (use_ref == 2) { a.feat_c = fc.data(); a.feat_f = ff.data(); a.perm = perm.data(); }
   if (use_ref != 1) {
     hipemu::launch(grid, 256, FB_LDS_FLOATS * sizeof(float), [&] { k_ngp_field_bwd_mfma(a); });
+    for (int k = 0; k < 6; ++k)
+      for (int i = 0; i < glen[k]; ++i) gout[k][i] += (float)((double)gacc[k][i] * SF_FIX_INV);
     return;
   }
   // reference: per-point math (ngp_device.h), serial
@@ -122,9 +131,10 @@ extern "C" int emu_bin_scatter(const int32_t* h_offsets, uint32_t L, float S, ui
   }
   std::vector<uint32_t> cursor(tb, 0);
   std::vector<f32x4> ent((size_t)tb * cap);
-  b.lv = lv; b.bound = bound; b.aabb = aabb; b.dfeat = dfeat; b.gtable = gtable; b.cursor = cursor.data(); b.ent = ent.data();
+  std::vector<long long> gacc((size_t)h_offsets[L] * 2, 0);           // fixed-point sums (sf_dev.h), added to gtable at the end
+  b.lv = lv; b.bound = bound; b.aabb = aabb; b.dfeat = dfeat; b.gtable = gacc.data(); b.gtable_f = gtable; b.thr = sf_fix_thr(8.0 * P); b.cursor = cursor.data(); b.ent = ent.data();
   b.T2 = T2; b.first_level = first_level; b.P_stride = P; b.cap = cap;
-  r.lv = lv; r.gtable = gtable; r.cursor = cursor.data(); r.ent = ent.data(); r.first_level = first_level; r.cap = cap;
+  r.lv = lv; r.gtable = gacc.data(); r.gtable_f = gtable; r.thr = b.thr; r.cursor = cursor.data(); r.ent = ent.data(); r.first_level = first_level; r.cap = cap;
   const uint32_t Nc = (N + chunks - 1) / chunks;
   for (uint32_t c = 0; c * Nc < N; ++c) {
     const uint32_t n0 = c * Nc, nn = n0 + Nc <= N ? Nc : N - n0;
@@ -133,5 +143,6 @@ extern "C" int emu_bin_scatter(const int32_t* h_offsets, uint32_t L, float S, ui
     hipemu::launch(tb, SBR_THREADS, 0, [&] { k_ngp_bin_reduce(r); });
     for (uint32_t k = 0; k < tb; ++k) if (cursor[k]) return 2;          // the reducer leaves every cursor at zero
   }
+  for (size_t i = 0; i < gacc.size(); ++i) gtable[i] += (float)((double)gacc[i] * SF_FIX_INV);
   return 0;
 }

@@ -35,7 +35,7 @@ def test_two_ranks_strong_scaling_dry_run():
 
 
 def test_bench_spawns_its_own_ranks():
-    """`python bench.py --gpus 2` without a launcher (how the driver invokes the N = 1 bench): bench.py re-execs itself under
+    """`python bench.py --gpus 2` without a launcher (how the driver invokes the N = 1 bench): bench.py starts itself under
     torch.distributed.run, one rank per GPU (the reference spawns its ranks itself too: demo.py:180, :22)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SF_BENCH_BACKEND"] = "gloo"
@@ -103,6 +103,38 @@ def test_default_max_thres_is_drawn_per_step():
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert "drawn per step" in res["config"]["workload"] and res["config"]["unet_evals_per_step"] == 51 and res["value"] > 0
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after exactly --steps timed steps, the last step's outputs and the NGP parameters after its optimiser step land
+    in DIR as float32 .npy files (64 MB at most in all), listed in the JSON line.  It is the LAST TIMED step's: 1 warm-up + 2 timed steps
+    and 2 warm-up + 1 timed step end on the same third step and must dump the same arrays, bit for bit (seeded inputs, order-independent
+    gradient sums), while 1 warm-up + 1 timed step must not."""
+    import numpy as np
+
+    def bench(tag, steps, warmup):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--max-thres", "0.06",
+               "--no-cpu-baseline", "--no-traffic", "--no-also-measured", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert res["steps"] == steps and res["ms_per_step"] > 0
+        arrays = res["dumped_outputs"]["arrays"]
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in arrays)
+        return arrays, {n: np.load(d / (n + ".npy")) for n in arrays}
+
+    arrays, a = bench("a", 2, 1)
+    assert {"loss_input_view", "loss_novel_view", "novel_rgb", "pred_img", "ngp.encoder.embeddings"} <= set(arrays)
+    for name, entry in arrays.items():
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all(), name
+        assert list(a[name].shape) == entry["shape"] and not entry["sampled"], name
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert arrays["pred_img"]["shape"] == [1, 3, 256, 256] and arrays["ngp.encoder.embeddings"]["shape"] == [929336, 2]
+    _, b = bench("b", 1, 2)
+    assert not [n for n in a if not np.array_equal(a[n], b[n])]
+    _, c = bench("c", 1, 1)
+    assert not np.array_equal(a["ngp.encoder.embeddings"], c["ngp.encoder.embeddings"])
 
 
 _HELPERS_ON_RCCL = r"""

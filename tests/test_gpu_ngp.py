@@ -252,6 +252,8 @@ def test_render_full_size_properties(golden):
     assert 0.05 < float(ws.mean()) < 0.95
     for a, b, c in zip(gr1, gr2, gr3):                                           # backward is linear in the upstream grads
         assert ((a + b) - c).norm() <= 1e-3 * c.norm() + 1e-6
+    _, gr4 = fwd_bwd(g1, w1)                                                     # deterministic bwd: fixed-point gradient sums
+    assert all(torch.equal(a, b) for a, b in zip(gr1, gr4))
     # PSNR against the oracle render of a 64x64 view (>= 50 dB)
     o2, d2 = ngp_ref.circle_rays(64, view=20)
     n2 = o2.shape[0]

@@ -105,3 +105,42 @@ def test_binned_scatter_matches_per_corner_adds(case):
         got = run(0, chunks, grid)
         err = float((got - ref).abs().max()) / float(ref.abs().max())
         assert err < 1e-5, (case, chunks, grid, err)
+
+
+def test_binned_scatter_keeps_large_and_non_finite_contributions():
+    """The table gradient sums addends below a threshold in 64-bit fixed point (sf_dev.h sf_grad_add) and adds every other one -- large,
+    Inf, NaN -- to the fp32 table as before: contributions far above the threshold still match the per-corner fp32 adds, and a NaN
+    feature gradient still reaches the table (it is neither dropped nor turned into a finite number)."""
+    lib = _lib()
+    g = torch.Generator().manual_seed(2)
+    N, T2 = 150, 22
+    P = N * T2
+    o, d = ngp_ref.circle_rays(13, view=1)
+    o, d = o[:N].contiguous(), d[:N].contiguous()
+    z = (torch.rand(N, T2, generator=g) * 9.0 + 1.0).sort(1).values.contiguous()
+    L, S = 16, float(np.log2(ngp_ref.per_level_scale(4)))
+    sizes = [min(1 << 12, (int(np.ceil(16 * 2.0 ** (l * S))) + 1) ** 3) for l in range(L)]
+    offs = torch.tensor(np.concatenate([[0], np.cumsum([(n + 7) // 8 * 8 for n in sizes])]), dtype=torch.int32)
+    aabb = torch.tensor([-4.0] * 3 + [4.0] * 3)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    first = 6
+
+    def run(dfeat, use_ref):
+        tab = torch.zeros(int(offs[-1]), 2)
+        rc = lib.emu_bin_scatter(ptr(offs), C.c_uint32(L), C.c_float(S), C.c_uint32(16), C.c_uint32(0), C.c_float(4.0), ptr(o), ptr(d),
+                                 ptr(aabb), ptr(z), ptr(dfeat), C.c_uint32(N), C.c_uint32(T2), C.c_uint32(first), C.c_uint32(16384),
+                                 C.c_uint32(2), C.c_uint32(3), C.c_int(use_ref), ptr(tab))
+        assert rc == 0, rc
+        return tab
+
+    dfeat = torch.randn(L, P, 2, generator=g)
+    big = torch.rand(L, P, 1, generator=g) < 0.2
+    dfeat = torch.where(big, dfeat * 1e6, dfeat).contiguous()        # threshold here: 8 (sf_fix_thr(8 P)); these are ~1e6
+    ref, got = run(dfeat, 1), run(dfeat, 0)
+    assert float((got - ref).abs().max()) / float(ref.abs().max()) < 1e-5
+    dfeat[first + 2, 5 * T2 + 3, 0] = float("nan")
+    ref, got = run(dfeat, 1), run(dfeat, 0)
+    nan_g, nan_r = torch.isnan(got), torch.isnan(ref)
+    assert bool(nan_g.any()) and not bool((nan_g & ~nan_r).any())      # NaN where the reference has it (a zero-weight corner may be skipped)
+    ok = ~nan_r
+    assert float((got[ok] - ref[ok]).abs().max()) / float(ref[ok].abs().max()) < 1e-5
