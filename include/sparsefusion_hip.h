@@ -173,6 +173,39 @@ typedef struct {
 int sf_ngp_density(const sf_ngp_field* f, const float* xyz, uint32_t P,
                    float* sigma, float* albedo, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Mesh export (renderer_df.py:122-165 export_mesh, nerf/utils.py:174-204     */
+/* extract_fields / extract_geometry) -- see DESIGN.md section 9.            */
+/* Volumes are [nx][ny][nz] f32, point p = (i*ny + j)*nz + k.                */
+/* ------------------------------------------------------------------------ */
+
+/* sigma[(i*ny + j)*nz + k] = density at (ax[i], ay[j], az[k]); bit-identical to sf_ngp_density on the same points.
+ * 1 <= nx, ny, nz and nx*ny*nz < 2^31. */
+int sf_ngp_density_lattice(const sf_ngp_field* f, const float* ax, const float* ay, const float* az,
+                           uint32_t nx, uint32_t ny, uint32_t nz, float* sigma, void* stream);
+
+/* Separable Gaussian of scipy.ndimage.gaussian_filter (mode 'reflect', radius int(truncate*sigma + 0.5) <= 64, taps in
+ * double, one pass per axis in the order 0, 1, 2, each output rounded to f32).  in and out must not alias.  stats (or NULL)
+ * receives {mean, population std} of out in double, reduced in a fixed order (bit-reproducible).
+ * workspace: sf_gaussian3d_workspace_bytes(nx, ny, nz) bytes (0: unsupported shape). */
+uint64_t sf_gaussian3d_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int sf_gaussian3d(const float* in, float* out, uint32_t nx, uint32_t ny, uint32_t nz,
+                  float sigma, float truncate, double* stats, void* workspace,
+                  uint64_t workspace_bytes, void* stream);
+
+/* Marching cubes of vol at iso (a corner is inside when v < iso; Lorensen / Bourke tables).  sf_mc_count classifies and
+ * writes counts2 = {V, F}; sf_mc_emit (same vol, iso and untouched workspace, after sf_mc_count) writes verts [V,3] in index
+ * coordinates and faces [F,3] (0-based), in the canonical order: vertices point-major (x-major), then edge axis x < y < z;
+ * faces cell-major (x-major), then table order; faces look toward decreasing values.  Rejects lattices with
+ * 3*nx*ny*nz >= 2^31 or 5*(nx-1)*(ny-1)*(nz-1) >= 2^31 (V or F could overflow int32).
+ * workspace: sf_mc_workspace_bytes(nx, ny, nz) bytes (0: unsupported shape). */
+uint64_t sf_mc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int sf_mc_count(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float iso,
+                void* workspace, uint64_t workspace_bytes, uint32_t* counts2, void* stream);
+int sf_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float iso,
+               void* workspace, uint64_t workspace_bytes, float* verts, int32_t* faces,
+               void* stream);
+
 /* Full training/eval render of N rays with T coarse + T fine samples (T<=64).
  * lin [T] = linspace(0,1,T); u_coarse [N,T] in [0,1) or NULL (perturb=False);
  * u_fine: uniforms for the inverse-CDF draw, row n at u_fine + n*u_fine_row_stride

@@ -1,0 +1,157 @@
+// Mesh export (NeRFRenderer.export_mesh, external/nerf/renderer_df.py:122-165; extract_fields / extract_geometry,
+// external/nerf/utils.py:174-204): the NGP density on a lattice, the separable Gaussian + volume statistics and marching cubes
+// of mesh_kernels.h.  Host entry points declared in include/sparsefusion_hip.h.  See DESIGN.md section 9.
+#include "sf_common.h"
+#include "mesh_kernels.h"
+#include "ngp_field_lds.h"
+
+// sigma at (ax[i], ay[j], az[k]) -> sigma[(i * ny + j) * nz + k], straight from the lattice index (no point buffer).  The per-point
+// code is k_ngp_field's (ngp_render.hip): weights in LDS, the same encode / MLP / activation, so a lattice value is bit-identical
+// to sf_ngp_density on the same fp32 point.  The barrier at the top of each round of the grid-stride loop keeps the compiler
+// from hoisting the loop-invariant LDS weight reads out of the loop (which would pin them in registers and spill).
+__global__ __launch_bounds__(256) void k_ngp_lattice(FieldPtrs f, NgpLevels lv, const float* __restrict__ ax, const float* __restrict__ ay,
+                                                     const float* __restrict__ az, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                     float* __restrict__ sigma) {
+  __shared__ __attribute__((aligned(16))) float W[NGP_WTOTAL];
+  load_weights_lds(W, f);
+  const uint64_t P = (uint64_t)nx * ny * nz;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < P; base += (uint64_t)gridDim.x * blockDim.x) {
+    __syncthreads();
+    const uint64_t p = base + threadIdx.x;
+    if (p >= P) continue;
+    const uint32_t k = (uint32_t)(p % nz), j = (uint32_t)((p / nz) % ny), i = (uint32_t)(p / ((uint64_t)ny * nz));
+    const float x[3] = {ax[i], ay[j], az[k]};
+    float x01[3];
+    const bool inside = ngp_unit(x, f.bound, x01);
+    float feat[NGP_FEAT], h1[NGP_HID], h2[NGP_HID], out[NGP_OUT];
+    ngp_encode(lv, f.table, x01, inside, feat);
+    ngp_mlp_forward(W, feat, h1, h2, out);
+    sigma[p] = expf(out[0] + ngp_blob(x));
+  }
+}
+
+static bool mesh_dims_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
+  return nx >= 1 && ny >= 1 && nz >= 1 && (uint64_t)nx * ny * nz < (1ull << 31);
+}
+
+extern "C" int sf_ngp_density_lattice(const sf_ngp_field* f, const float* ax, const float* ay, const float* az, uint32_t nx,
+                                      uint32_t ny, uint32_t nz, float* sigma, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!mesh_dims_ok(nx, ny, nz)) SF_FAIL(SF_ERR_INVALID, "ngp_density_lattice: need 1 <= nx, ny, nz and nx*ny*nz < 2^31");
+  if (!ax || !ay || !az || !sigma) SF_FAIL(SF_ERR_INVALID, "ngp_density_lattice: null pointer");
+  NgpLevels lv;
+  if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
+  k_ngp_lattice<<<sf_grid_cap(sf_div_up((uint64_t)nx * ny * nz, 256)), 256, 0, st>>>(sf_ngp_field_ptrs(f), lv, ax, ay, az, nx, ny, nz,
+                                                                                    sigma);
+  SF_CHECK_LAUNCH("ngp_density_lattice");
+  return SF_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- Gaussian
+static uint64_t align256(uint64_t b) { return (b + 255) & ~255ull; }
+
+static uint32_t gauss_stat_wgs(uint32_t nx, uint32_t ny, uint32_t nz) {
+  const uint64_t tiles = (uint64_t)nx * ny * sf_div_up(nz, GS_NT);
+  return (uint32_t)(tiles < GS_STAT_WG ? tiles : GS_STAT_WG);
+}
+
+extern "C" uint64_t sf_gaussian3d_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz) {
+  if (!mesh_dims_ok(nx, ny, nz)) return 0;
+  return align256((uint64_t)nx * ny * nz * sizeof(float)) + align256((uint64_t)gauss_stat_wgs(nx, ny, nz) * 2 * sizeof(double));
+}
+
+extern "C" int sf_gaussian3d(const float* in, float* out, uint32_t nx, uint32_t ny, uint32_t nz, float sigma, float truncate,
+                             double* stats, void* ws, uint64_t ws_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!mesh_dims_ok(nx, ny, nz)) SF_FAIL(SF_ERR_INVALID, "gaussian3d: need 1 <= nx, ny, nz and nx*ny*nz < 2^31");
+  if (!in || !out || !ws) SF_FAIL(SF_ERR_INVALID, "gaussian3d: null pointer");
+  if (in == out) SF_FAIL(SF_ERR_INVALID, "gaussian3d: in and out must not alias");
+  if (ws_bytes < sf_gaussian3d_workspace_bytes(nx, ny, nz)) SF_FAIL(SF_ERR_INVALID, "gaussian3d: workspace too small");
+  GaussTaps taps;
+  if (!gs_make_taps(sigma, truncate, &taps))
+    SF_FAIL(SF_ERR_INVALID, "gaussian3d: need sigma > 0, truncate >= 0 and radius int(truncate * sigma + 0.5) <= %d", GS_RMAX);
+  float* tmp = (float*)ws;
+  double* partial = (double*)((char*)ws + align256((uint64_t)nx * ny * nz * sizeof(float)));
+  const uint32_t segx = sf_div_up(nx, GS_SEG), segy = sf_div_up(ny, GS_SEG);
+  k_gauss_strided<<<sf_div_up((uint64_t)segx * ny * nz, GS_NT), GS_NT, 0, st>>>(in, out, 1, nx, ny * nz, taps);       // axis 0
+  SF_CHECK_LAUNCH("gaussian3d axis 0");
+  k_gauss_strided<<<sf_div_up((uint64_t)nx * segy * nz, GS_NT), GS_NT, 0, st>>>(out, tmp, nx, ny, nz, taps);          // axis 1
+  SF_CHECK_LAUNCH("gaussian3d axis 1");
+  const uint32_t nwg = gauss_stat_wgs(nx, ny, nz);
+  k_gauss_rows<<<nwg, GS_NT, 0, st>>>(tmp, out, (uint64_t)nx * ny, nz, taps, stats ? partial : nullptr);             // axis 2
+  SF_CHECK_LAUNCH("gaussian3d axis 2");
+  if (stats) {
+    k_gauss_stats<<<1, GS_NT, 0, st>>>(partial, nwg, (uint64_t)nx * ny * nz, stats);
+    SF_CHECK_LAUNCH("gaussian3d stats");
+  }
+  return SF_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------------- marching cubes
+// Workspace: code u16 [N] | vbase u32 [N] | bsum u32 [2 * nblk] | boff u32 [2 * nblk]
+struct McWs { uint16_t* code; uint32_t* vbase; uint32_t* bsum; uint32_t* boff; };
+
+static uint32_t mc_blocks(uint32_t nx, uint32_t ny, uint32_t nz) { return sf_div_up((uint64_t)nx * ny * nz, MC_BLOCK); }
+
+// V <= 3 N and F <= 5 cells: both must fit in int32 before anything runs (nothing is read back)
+static bool mc_dims_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
+  if (!mesh_dims_ok(nx, ny, nz)) return false;
+  const uint64_t N = (uint64_t)nx * ny * nz, cells = (uint64_t)(nx - 1) * (ny - 1) * (nz - 1);
+  return 3 * N < (1ull << 31) && 5 * cells < (1ull << 31);
+}
+
+static McWs mc_ws(void* ws, uint32_t nx, uint32_t ny, uint32_t nz) {
+  const uint64_t N = (uint64_t)nx * ny * nz, nb = mc_blocks(nx, ny, nz);
+  char* b = (char*)ws;
+  McWs w;
+  w.code = (uint16_t*)b;
+  b += align256(N * 2);
+  w.vbase = (uint32_t*)b;
+  b += align256(N * 4);
+  w.bsum = (uint32_t*)b;
+  b += align256(nb * 8);
+  w.boff = (uint32_t*)b;
+  return w;
+}
+
+extern "C" uint64_t sf_mc_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz) {
+  if (!mc_dims_ok(nx, ny, nz)) return 0;
+  const uint64_t N = (uint64_t)nx * ny * nz, nb = mc_blocks(nx, ny, nz);
+  return align256(N * 2) + align256(N * 4) + 2 * align256(nb * 8);
+}
+
+static int mc_check(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, void* ws, uint64_t ws_bytes, const char* what) {
+  if (!mc_dims_ok(nx, ny, nz)) SF_FAIL(SF_ERR_INVALID, "%s: need 1 <= nx, ny, nz, 3*nx*ny*nz < 2^31 and 5*(nx-1)*(ny-1)*(nz-1) < 2^31", what);
+  if (!vol || !ws) SF_FAIL(SF_ERR_INVALID, "%s: null pointer", what);
+  if (ws_bytes < sf_mc_workspace_bytes(nx, ny, nz)) SF_FAIL(SF_ERR_INVALID, "%s: workspace too small", what);
+  return SF_OK;
+}
+
+extern "C" int sf_mc_count(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void* ws, uint64_t ws_bytes,
+                           uint32_t* counts2, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mc_check(vol, nx, ny, nz, ws, ws_bytes, "mc_count")) return rc;
+  if (!counts2) SF_FAIL(SF_ERR_INVALID, "mc_count: null pointer");
+  const McWs w = mc_ws(ws, nx, ny, nz);
+  const uint32_t nb = mc_blocks(nx, ny, nz);
+  const McDims d{nx, ny, nz};
+  k_mc_classify<<<nb, MC_NT, 0, st>>>(vol, d, iso, w.code, w.bsum);
+  SF_CHECK_LAUNCH("mc_classify");
+  k_mc_scan<<<1, MC_NT, 0, st>>>(w.bsum, nb, w.boff, counts2);
+  SF_CHECK_LAUNCH("mc_scan");
+  return SF_OK;
+}
+
+extern "C" int sf_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void* ws, uint64_t ws_bytes, float* verts,
+                          int32_t* faces, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mc_check(vol, nx, ny, nz, ws, ws_bytes, "mc_emit")) return rc;
+  const McWs w = mc_ws(ws, nx, ny, nz);
+  const uint32_t nb = mc_blocks(nx, ny, nz);
+  const McDims d{nx, ny, nz};
+  k_mc_emit_verts<<<nb, MC_NT, 0, st>>>(vol, d, iso, w.code, w.boff, verts, w.vbase);
+  SF_CHECK_LAUNCH("mc_emit_verts");
+  k_mc_emit_faces<<<nb, MC_NT, 0, st>>>(d, w.code, w.boff, w.vbase, faces);
+  SF_CHECK_LAUNCH("mc_emit_faces");
+  return SF_OK;
+}

@@ -31,6 +31,7 @@ static inline float sf_fix_thr(double max_addends) {      // host: largest power
 #define SF_DEV inline
 #define SF_DYN_LDS(name) char* name = hipemu::dyn_smem()
 #define SF_SHARED static
+#define SF_CONSTANT static const
 static inline void sf_sync() { hipemu::syncthreads(); }
 template <class T>
 static inline T sf_shfl_xor(T v, int m) { return hipemu::shfl_xor(v, m); }
@@ -146,6 +147,7 @@ static const uint32_t sf_zero128[32] __attribute__((aligned(128))) = {0};
 #define SF_DEV __device__ __forceinline__
 #define SF_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name[]
 #define SF_SHARED __shared__
+#define SF_CONSTANT __constant__ static const      // read-only tables indexed per lane (constant address space)
 SF_DEV void sf_sync() { __syncthreads(); }
 template <class T>
 SF_DEV T sf_shfl_xor(T v, int m) { return __shfl_xor(v, m, 64); }

@@ -181,6 +181,30 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     @torch.no_grad()
+    def export_mesh(self, path, resolution=None, S=128):
+        """Geometry export of renderer_df.py:122-165 (its texture step is commented out there): the density on an R^3 lattice
+        over [-bound, bound]^3 (torch.linspace on the CPU, x-major), PyMCubes' Gaussian smoothing (sigma 1.5), the level
+        mean + 0.25 * std of the smoothed volume (float64), marching cubes, and `path/mcubes_mesh.obj` in index coordinates --
+        all on the GPU (sparsefusion_amd.mesh).  Returns (vertices [V, 3] float32 in world coordinates idx / (R - 1) * 2 * bound
+        - bound, faces [F, 3] int32) on the field's device.
+
+        Deviations from the reference, on purpose: `resolution=None` means 128 (the reference's effective value: it overrides
+        every resolution with 128) and an explicit resolution is honoured; the returned world coordinates use `bound` (the
+        reference's unused `vertices / (R - 1) * 2 - 1` ignores it); it needs no occupancy-grid state, so it also runs with
+        cuda_ray=False (the reference reads mean_density / density_bitfield, which exist only with cuda_ray).  `S` is accepted
+        for call compatibility: the lattice is evaluated without a point buffer, so there are no slabs to bound.  The marching
+        cubes' order and winding are this library's own (PyMCubes is not available to pin against)."""
+        from .. import mesh
+        R = 128 if resolution is None else int(resolution)
+        sigmas = mesh.density_lattice(self, R, self.bound)
+        smooth, stats = mesh.smooth_gaussian(sigmas, sigma=1.5, return_stats=True)
+        mean, std = (float(x) for x in stats.cpu())
+        vertices, faces = mesh.marching_cubes(smooth, mean + std * 0.25)
+        os.makedirs(path, exist_ok=True)
+        mesh.export_obj(vertices, faces, os.path.join(path, 'mcubes_mesh.obj'))
+        return vertices / (R - 1.0) * (2 * self.bound) - self.bound, faces
+
+    @torch.no_grad()
     def update_extra_state(self, decay=0.95, S=128, noise=None):
         """EMA update of the cascaded density grid, its bitfield and the mean sample count (renderer_df.py:586-638).
 

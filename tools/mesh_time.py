@@ -1,0 +1,116 @@
+"""Per-stage times of NeRFRenderer.export_mesh on the GPU (torch events around each stage, median of --reps runs after one warm-up)
+next to the CPU pipeline it is tested against (scipy gaussian_filter + numpy level + tests/mesh_ref.py marching cubes) on the
+same field.  One JSON line per resolution.
+
+    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+from ngp_common import BOUND, params_from_cfg      # noqa: E402
+import mesh_ref                                    # noqa: E402
+from sparsefusion_amd import mesh                  # noqa: E402
+from sparsefusion_amd.nerf import NeRFNetwork, get_default_torch_ngp_opt      # noqa: E402
+
+
+def gpu_run(net, R, path):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+    torch.cuda.synchronize()
+    ev[0].record()
+    vol = mesh.density_lattice(net, R, BOUND)
+    ev[1].record()
+    sm, stats = mesh.smooth_gaussian(vol, 1.5, return_stats=True)
+    ev[2].record()
+    mean, std = (float(x) for x in stats.cpu())
+    v, f = mesh.marching_cubes(sm, mean + std * 0.25)       # classify + scan, counts read back, emit
+    ev[3].record()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mesh.export_obj(v, f, path)
+    t_obj = (time.perf_counter() - t0) * 1e3
+    return dict(lattice=ev[0].elapsed_time(ev[1]), gauss_stats=ev[1].elapsed_time(ev[2]), mc=ev[2].elapsed_time(ev[3]), obj=t_obj,
+                V=int(v.shape[0]), F=int(f.shape[0])), vol
+
+
+def mc_split(sm, iso):
+    """classify + scan and emit timed separately through the C ABI (the same calls marching_cubes makes)."""
+    from sparsefusion_amd import _lib
+    lib = _lib.lib()
+    nx, ny, nz = sm.shape
+    wb = lib.sf_mc_workspace_bytes(nx, ny, nz)
+    work = torch.empty(wb, dtype=torch.uint8, device=sm.device)
+    counts = torch.empty(2, dtype=torch.int32, device=sm.device)
+    st = _lib.stream_ptr()
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    e[0].record()
+    _lib.check(lib.sf_mc_count(_lib.ptr(sm), nx, ny, nz, iso, _lib.ptr(work), wb, _lib.ptr(counts), st))
+    e[1].record()
+    V, F = (int(c) for c in counts.cpu())
+    verts = torch.empty(V, 3, device=sm.device)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=sm.device)
+    e2 = torch.cuda.Event(enable_timing=True)
+    e2.record()
+    _lib.check(lib.sf_mc_emit(_lib.ptr(sm), nx, ny, nz, iso, _lib.ptr(work), wb, _lib.ptr(verts), _lib.ptr(faces), st))
+    e[2].record()
+    torch.cuda.synchronize()
+    return e[0].elapsed_time(e[1]), e2.elapsed_time(e[2])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, nargs="+", default=[128, 256])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-cpu", action="store_true")
+    a = ap.parse_args()
+    golden = torch.load(os.path.join(ROOT, "tests", "golden", "ngp_render.pt"))
+    p = params_from_cfg(golden["teacher"]["cfg"])
+    net = NeRFNetwork(get_default_torch_ngp_opt())
+    net.load_state_dict({k: p[k] for k in net.state_dict().keys()})
+    net = net.to("cuda:0").eval()
+    tmp = tempfile.mkdtemp()
+    for R in a.res:
+        runs = []
+        with torch.no_grad():
+            for i in range(a.reps + 1):
+                r, vol = gpu_run(net, R, os.path.join(tmp, "m.obj"))
+                if i:
+                    runs.append(r)
+            sm, stats = mesh.smooth_gaussian(vol, 1.5, return_stats=True)
+            iso = float(stats[0] + 0.25 * stats[1])
+            splits = [mc_split(sm, iso) for _ in range(a.reps + 1)][1:]
+            t0 = time.perf_counter()
+            net.export_mesh(tmp, resolution=R)
+            torch.cuda.synchronize()
+            total = (time.perf_counter() - t0) * 1e3
+        med = {k: statistics.median(r[k] for r in runs) for k in ("lattice", "gauss_stats", "mc", "obj")}
+        out = dict(R=R, gpu_ms=dict(lattice=med["lattice"], gauss_stats=med["gauss_stats"],
+                                    classify_scan=statistics.median(s[0] for s in splits), emit=statistics.median(s[1] for s in splits),
+                                    mc_with_readback=med["mc"]), obj_write_ms=med["obj"], export_mesh_wall_ms=total,
+                   V=runs[0]["V"], F=runs[0]["F"])
+        if not a.no_cpu:
+            v = vol.cpu().numpy()
+            t0 = time.perf_counter()
+            s64 = mesh_ref.smooth_gaussian(v, 1.5)
+            t1 = time.perf_counter()
+            lvl = mesh_ref.iso_level(s64)
+            t2 = time.perf_counter()
+            cv, cf = mesh_ref.marching_cubes(s64.astype(np.float32), lvl)
+            t3 = time.perf_counter()
+            out["cpu_ms"] = dict(gaussian=(t1 - t0) * 1e3, stats=(t2 - t1) * 1e3, marching_cubes=(t3 - t2) * 1e3)
+            out["cpu_V"], out["cpu_F"] = int(cv.shape[0]), int(cf.shape[0])
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
