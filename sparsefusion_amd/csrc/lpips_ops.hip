@@ -76,10 +76,14 @@ __global__ __launch_bounds__(256) void k_pool_bwd(const float* __restrict__ dout
 
 // ---- LPIPS head ---------------------------------------------------------------------------------------------
 // feats [2V, HW, C]: samples 0..V-1 = in0 (gradient flows), V..2V-1 = in1.  One wave per pixel.
-//   u = f0 / (|f0| + eps), v = f1 / (|f1| + eps), d = sum_c w_c (u_c - v_c)^2, out[s] += mean_pixels d
+//   u = f0 / (|f0| + eps), v = f1 / (|f1| + eps), d = sum_c w_c (u_c - v_c)^2, acc[s] += mean_pixels d
+// The workgroups of all five layers meet in acc[s]: a 2^-44 fixed-point integer, so that the sum does not depend on the order in which
+// they arrive (an fp32 atomic here made the distance, and every loss built on it, differ in its last bits from run to run);
+// k_lpips_head_sum turns it into the float the caller reads.
 #define LPIPS_EPS 1e-10f
+#define LPIPS_FIX_ONE 17592186044416.0          // 2^44: a distance is O(1), a workgroup's share of it is kept to 6e-14
 __global__ __launch_bounds__(256) void k_lpips_head_fwd(const float* __restrict__ feats, const float* __restrict__ w,
-                                                        float* __restrict__ out, int V, int HW, int C) {
+                                                        long long* __restrict__ out, int V, int HW, int C) {
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int per_sample_blocks = gridDim.x / V;
@@ -110,9 +114,15 @@ __global__ __launch_bounds__(256) void k_lpips_head_fwd(const float* __restrict_
   }
   if (lane == 0) red[wv] = acc;
   __syncthreads();
-  if (threadIdx.x == 0)
-    (void)__builtin_amdgcn_global_atomic_fadd_f32((__attribute__((address_space(1))) float*)(out + s),
-                                                  (red[0] + red[1] + red[2] + red[3]) / (float)HW);
+  if (threadIdx.x == 0) {
+    const float part = (red[0] + red[1] + red[2] + red[3]) / (float)HW;
+    (void)atomicAdd(reinterpret_cast<unsigned long long*>(out + s), (unsigned long long)__double2ll_rn((double)part * LPIPS_FIX_ONE));
+  }
+}
+
+__global__ __launch_bounds__(64) void k_lpips_head_sum(const long long* __restrict__ acc, float* __restrict__ out, int V) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s < V) out[s] = (float)((double)acc[s] * (1.0 / LPIPS_FIX_ONE));
 }
 
 // dfeat[s, p, :] = gscale[s] / HW * d d_p / d f0:  a_c = 2 w_c (u_c - v_c);  df = a / n - f0 * (a . f0) / (n^2 |f0|)
@@ -213,11 +223,18 @@ int sf_plan_extra_op(const sf_op* opp, void* stream) {
     }
     case SF_OP_LPIPS: {
       const int V = op.i[0], HW = op.i[1], C = op.i[2];
+      if (op.flags == 2) {                                   // the accumulated distances p[2] (fixed point) -> p[3] (float)
+        if (V < 1 || !op.p[2] || !op.p[3] || ((uintptr_t)op.p[2] & 7)) SF_FAIL(SF_ERR_INVALID, "lpips head sum: bad operands");
+        k_lpips_head_sum<<<(unsigned)sf_div_up((uint64_t)V, 64), 64, 0, st>>>((const long long*)op.p[2], (float*)op.p[3], V);
+        SF_CHECK_LAUNCH("lpips_head_sum");
+        return SF_OK;
+      }
       if (V < 1 || C % 4 || !op.p[0] || !op.p[1] || !op.p[3]) SF_FAIL(SF_ERR_INVALID, "lpips head: bad operands");
       if (op.flags == 0) {
+        if ((uintptr_t)op.p[3] & 7) SF_FAIL(SF_ERR_INVALID, "lpips head: the accumulator is a 64-bit integer per sample");
         int per = sf_div_up((uint64_t)HW, 4);
         if (per > 256) per = 256;                            // one atomic per workgroup: keep them few
-        k_lpips_head_fwd<<<V * per, 256, 0, st>>>((const float*)op.p[0], (const float*)op.p[1], (float*)op.p[3], V, HW, C);
+        k_lpips_head_fwd<<<V * per, 256, 0, st>>>((const float*)op.p[0], (const float*)op.p[1], (long long*)op.p[3], V, HW, C);
       } else {
         if (!op.p[2]) SF_FAIL(SF_ERR_INVALID, "lpips head backward: missing upstream gradient");
         k_lpips_head_bwd<<<sf_grid_cap(sf_div_up((uint64_t)V * HW, 4)), 256, 0, st>>>(

@@ -77,9 +77,12 @@ class _LpipsPlan(_Plan):
             self.conv_out.append(y)
             h = y
         self.taps.append((h, H))
-        self.dist = _T(self.zero.alloc(V * 4), V, 1)               # accumulated with one atomic per workgroup: zeroed per run
+        # one integer atomic (2^-44 fixed point: order independent) per workgroup of the five heads, zeroed per run; then -> float
+        acc = self.zero.alloc(V * 8)
+        self.dist = _T(self.zero.alloc(V * 4), V, 1)
         for k, (t, Hk) in enumerate(self.taps):
-            self.op(OP_LPIPS, 0, p=(t.ptr, self.wptr(f"lin{k}.model.1.weight"), 0, self.dist.ptr), i=(V, Hk * Hk, t.C))
+            self.op(OP_LPIPS, 0, p=(t.ptr, self.wptr(f"lin{k}.model.1.weight"), 0, acc), i=(V, Hk * Hk, t.C))
+        self.op(OP_LPIPS, 2, p=(0, 0, acc, self.dist.ptr), i=(V, 0, 0))
         memset_op.i[0] = (self.zero.off + 3) // 4
         self.op_array = (_lib.SfOp * len(self.ops))(*self.ops)
         if self.misc.buf is not None:

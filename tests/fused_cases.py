@@ -1,7 +1,16 @@
 """Shared cases of the fused UNet kernels (sparsefusion_amd/csrc/fused_kernels.h): the same op descriptors run either on
 CPU threads (backend "emu": tests/hostemu, kernel logic without a GPU) or through the C ABI on the GPU (backend "gpu":
-sf_plan_run), and are compared with a plain torch fp32 reference of the same op on bf16-rounded operands
-(GroupNorm / LayerNorm -> scale/shift -> SiLU -> conv, external/imagen_pytorch.py:641-662)."""
+sf_plan_run), and are compared with references of the same op (GroupNorm / LayerNorm -> scale/shift -> SiLU -> conv,
+external/imagen_pytorch.py:641-662).
+
+The conv cases (run_conv_case) carry two checks:
+  * the whole-tensor one: relative L2 < 4e-3 against a plain torch fp32 reference on bf16-rounded operands;
+  * the per-element one (conv_reference64 below): a float64 reference that rounds where the kernel rounds, and for EVERY output
+    element a bound derived from the roundings of the kernel's path -- which way an operand next to a rounding tie of the operand
+    type may legitimately go, fp32 accumulation in any order, the fp32 epilogue adds.  No constant of it is fitted to a kernel's
+    output; the measured margins of both backends are in profiles/fused_conv_parity_margins.log."""
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -34,6 +43,152 @@ def to_rows(x):            # NCHW -> [M, C]
     return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).contiguous()
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The per-element bound.  u = 2^-24 is the unit roundoff of fp32 round-to-nearest; an operation the ISA documents as accurate to
+# 1 ulp (v_exp_f32, v_rcp_f32, v_rsq_f32: "CDNA4 ISA", VOP1 transcendental accuracy) is 2 u.  Every term is first order in u.
+#
+# (a) the staged value  y = ((x - mean) * rstd * gamma + beta) * (scale + 1) + shift,  s = SiLU(y).
+#   The kernels evaluate it as x * A + Bv with A = rstd * gamma * (scale + 1) [* scale2] and Bv = (beta - A0 * mean) * (scale + 1) +
+#   shift (fused_conv3s.h consume(), fused_kernels.h build_table(), fused_conv4.h), the LayerNorm ones as (x - mean) * rstd * gamma
+#   + beta.  x * A and mean * A cancel, so a rounding acts on the magnitude of the TERMS, not of y:
+#       M  = ((|x| + |mean|) * rstd * |gamma| + |beta|) * |scale + 1| + |shift|.
+#   Roundings on the longest path through the affine (Bv of fused_conv3s.h): gamma * rstd, * mean, beta - ., scale + 1, * (scale + 1),
+#   + shift, the final fma, and mean's own double -> float: 8 = N_AFF.
+#   rstd = v_rsq((float) var + eps): 2 roundings + 1 ulp = 4 u on its argument, i.e. 2 u on rstd, rounded up to 3 u.
+#   The statistics come from fp32 sums; a chain of n additions (an fma counts as one) is off by at most n u sum|terms|.  Longest chains:
+#     GroupNorm, sum:          N_SUM = 16  (GN_SELF: <= 8 float4 per thread, 3 levels each pair-wise = NV + 2, then <= 6 shuffle levels, then doubles;
+#                                           GN_SLOTS: slot * scale, <= 8 slots per lane (<= 512 slots per group), 6 shuffle levels, then doubles)
+#     GroupNorm, sum of squares: N_SQ = 40 (GN_SELF: 4 chained fma per float4 = 32, + 6 shuffle levels; GN_SLOTS: as the sum)
+#     LayerNorm (two-pass, 16 float4 per thread): mean 16 + 2 + 5 + the division = N_SUM_LN = 24; sum of (x - mean)^2: 64 fma + 5 levels + the
+#                                           subtraction + the division <= N_SQ_LN = 72
+#   With r2 = E[x^2] / var (>= 1) and E|x| <= sqrt(E[x^2]):   |d mean| <= N_SUM u sqrt(E[x^2]),   d E[x^2] <= N_SQ u E[x^2],
+#     GroupNorm: d var <= d E[x^2] + 2 |mean| |d mean|   ->   d rstd / rstd = d var / (2 var) <= (N_SQ r2 + 2 N_SUM |mean| rstd sqrt(r2)) u / 2 =: R u
+#     LayerNorm: the squares are of (x - mean), all terms positive:  d var <= N_SQ_LN u var  ->  R = N_SQ_LN / 2  (d mean enters var in second order)
+#   (For GN_SLOTS the reference takes its statistics from the very fp32 slots the kernel is given, in float64, so the producer's own
+#   summation error is in neither.)  d mean moves y by rstd |gamma (scale + 1)| |d mean| <= N_SUM u M2 with M2 = sqrt(r2) |gamma (scale + 1)|.
+#       d(y) = u * ((N_AFF + 3 + R) * M + N_SUM * M2)  +  rstd |gamma (scale + 1)| * (dx + group mean of dx)
+#   dx is the uncertainty of a lazily evaluated source (split-K slabs + bias + residual: groups + 1 additions on sum|terms|; gate: one
+#   fma + one add; a GELU in front of the LayerNorm: see (c)); 0 for a plain source.
+#   SiLU as the kernels write it, y * v_rcp(1 + v_exp(y * -log2 e)): the product y * log2 e is off by u, which moves the exponential
+#   by |y| ln2 log2e u = |y| u; + 2 u (v_exp) + u (the add) + 2 u (v_rcp) + u (the product): s is off by (|y| + 6) u |s| on top of what
+#   d(y) does through the function.  That is carried by the LOCAL slope silu'(y) = sig(y) (1 + y (1 - sig(y))), with |silu''| <= 1/2 for the
+#   remainder.  (|silu'| <= 1.1 everywhere, but the slope is near 0 where s is small against M, and a small s has a small operand ulp: with the
+#   global constant those elements alone decide the ambiguous share, and the median bound / rms of the K = 18432 cases was 1.1e-3 .. 1.7e-3.)
+#       d(s) = |silu'(y)| d(y) + d(y)^2 / 4 + (|y| + 6) u |s|.
+# (b) the accumulation.  A product of two 16-bit operands is exact in fp32.  A term of the sum is rounded when it is added inside its
+#   MFMA (<= 32 additions: K = 32), with every later MFMA of its wave's chain (a split-K op gives each of its S slabs K / S of the sum, and
+#   every kernel splits a workgroup's share over >= 4 waves: <= ceil(K / (128 S)) steps), in the K-slice reduction in LDS (<= 8 slices) and
+#   in the slab sum (S):  c = ceil(K / (128 S)) + 32 + 8 + S.
+# (c) GELU (0.5 v (1 + erff(v / sqrt 2)), OCML erff <= 4 ulp of a value below 1 = 4 u absolute): 0.5 |v| (4 u + u) + 2 u |gelu| + the
+#   rounding of v / sqrt 2 through the slope: below 8 u |v|.  Its slope is at most 1.13.
+U24 = 2.0 ** -24
+N_AFF, N_SUM, N_SQ, N_SUM_LN, N_SQ_LN = 8, 16, 40, 24, 72
+AMB_SHARE_MAX, BOUND_MEDIAN_MAX = 0.05, 1e-3        # conditions of the reference alone (asserted): see run_conv_case
+# cases left on the whole-tensor norm alone (name -> reason); none: the GELU forms have a derived bound, (c) above
+NORM_CHECK_ONLY = {}
+
+
+def opnd_dtype(backend):
+    """The MFMA operand type of the build under test: the emulation is a bf16 build, the GPU library says what it is."""
+    return torch.bfloat16 if backend == "emu" else _lib.operand_dtype()
+
+
+def _rnd(x64, dt):                                     # fp32 -> operand type as the kernels convert, kept in float64
+    return x64.float().to(dt).double()
+
+
+def _gelu64(v):
+    return 0.5 * v * (1.0 + torch.erf(v * 0.7071067811865476))
+
+
+def _conv64(x_rows, w64, B, H, W):                     # [M, C] float64, [Cout, C, k, k] -> [M, Cout]
+    return to_rows(F.conv2d(nhwc(x_rows, B, H, W), w64, None, padding=w64.shape[-1] // 2))
+
+
+def staged_reference64(x, dx, B, HW, norm, G, gamma, beta, ssv, silu, eps, stats=None, pre_gelu=False):
+    """float64 value s of the conv's A operand before its rounding to the operand type, and the uncertainty d of the kernel's fp32
+    evaluation of it (derivation (a) above).  x, dx: [M, C] float64; stats: per (image, group) float64 (sum, sum of squares) the kernel
+    is handed (GN_SLOTS), else they are taken from x."""
+    M, C = x.shape
+    if norm == NONE:
+        y, dy = x, dx
+    else:
+        if norm == LN:
+            if pre_gelu:
+                dx = 1.13 * dx + 8 * U24 * x.abs()
+                x = _gelu64(x)
+            xg, dg = x.view(M, 1, C), dx.view(M, 1, C)
+        else:
+            xg = x.view(B, HW, G, C // G).permute(0, 2, 1, 3).reshape(B * G, 1, -1)        # [image x group][1][HW * Cg]
+            dg = dx.view(B, HW, G, C // G).permute(0, 2, 1, 3).reshape(B * G, 1, -1)
+        n = xg.shape[-1]
+        if stats is None:
+            s1, s2 = xg.sum(-1, keepdim=True), (xg * xg).sum(-1, keepdim=True)
+        else:
+            s1, s2 = stats[..., 0].reshape(-1, 1, 1), stats[..., 1].reshape(-1, 1, 1)
+        mean, ex2 = s1 / n, s2 / n
+        var = (ex2 - mean * mean).clamp(min=0)
+        rstd = (var + eps).rsqrt()
+        r2 = ex2 / var
+        back = (lambda t: t.expand_as(xg).reshape(M, C)) if norm == LN else \
+               (lambda t: t.expand_as(xg).reshape(B, G, HW, C // G).permute(0, 2, 1, 3).reshape(M, C))
+        mean, rstd, r2, dxm = back(mean), back(rstd), back(r2), back(dg.mean(-1, keepdim=True))
+        g64 = gamma.double()
+        b64 = beta.double() if beta is not None else torch.zeros(C, dtype=torch.float64)
+        if ssv is not None:
+            sc = (ssv[:, :C].double() + 1).repeat_interleave(HW, 0)
+            sh = ssv[:, C:].double().repeat_interleave(HW, 0)
+        else:
+            sc, sh = torch.ones(M, C, dtype=torch.float64), torch.zeros(M, C, dtype=torch.float64)
+        y = ((x - mean) * rstd * g64 + b64) * sc + sh
+        mag = ((x.abs() + mean.abs()) * rstd * g64.abs() + b64.abs()) * sc.abs() + sh.abs()
+        slope = rstd * (g64 * sc).abs()
+        nsum = N_SUM_LN if norm == LN else N_SUM
+        R = N_SQ_LN / 2 if norm == LN else (N_SQ * r2 + 2 * N_SUM * mean.abs() * rstd * r2.sqrt()) / 2
+        dy = U24 * ((N_AFF + 3 + R) * mag + nsum * r2.sqrt() * (g64 * sc).abs()) + slope * (dx + dxm)
+    if not silu:
+        return y, dy
+    sg = torch.sigmoid(y)
+    s = y * sg
+    return s, (sg * (1 + y * (1 - sg))).abs() * dy + dy * dy / 4 + (y.abs() + 6) * U24 * s.abs()
+
+
+def conv_reference64(s, d, w, dt, B, H, W, S=1):
+    """want (before the epilogue adds) and the per-element bound of the conv of the operand-rounded staged value: the rounding-tie
+    allowance and fp32 accumulation in any order ((b) above).  Returns want [M, Cout], bound, the ambiguous share of the operand."""
+    lo, hi, mid = _rnd(s - d, dt), _rnd(s + d, dt), _rnd(s, dt)
+    amb = hi - lo
+    w64 = _rnd(w.double(), dt)
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    c = math.ceil(K / (128 * S)) + 32 + 8 + S
+    want = _conv64(mid, w64, B, H, W)
+    ab = _conv64(torch.cat([amb, c * U24 * mid.abs()], 0), w64.abs(), 2 * B, H, W)
+    return want, ab[:s.shape[0]] + ab[s.shape[0]:], float((amb > 0).double().mean())
+
+
+def where_is(idx, Cout, B, H, W, WM, WN, tw):
+    """(image, row, column, channel) of flat output element idx and its place in the launch: tile, n-tile, fragment, lane, register
+    (D fragment of v_mfma_f32_16x16x32: lane l holds rows 4 (l >> 4) + r, column l & 15)."""
+    m, n = divmod(int(idx), Cout)
+    b, r, x = m // (H * W), (m % (H * W)) // W, m % W
+    TW = tw or W
+    TH = max(1, 16 * WM // TW)
+    p = (r % TH) * TW + x % TW
+    return (f"image {b} row {r} column {x} channel {n}: tile ({r // TH}, {x // TW}) n-tile {n // (16 * WN)} fragment (mi {p // 16}, ni {n // 16 % WN}) "
+            f"lane {n % 16 + 16 * (p % 16 // 4)} register {p % 4}")
+
+
+def check_elements(what, got, want, bound, Cout, B, H, W, WM, WN, tw):
+    """|got - want| <= bound for every element: (worst err / bound, None or the report of a failure)."""
+    err = (got.double() - want).abs()
+    ratio = err / bound.clamp(min=1e-300)
+    worst = int(ratio.argmax())
+    bad = int((err > bound).sum())
+    msg = None if bad == 0 else (f"{what}: {bad} of {err.numel()} elements outside their bound; worst err / bound {float(ratio.view(-1)[worst]):.3g} "
+                                 f"(err {float(err.view(-1)[worst]):.3g}) at {where_is(worst, Cout, B, H, W, WM, WN, tw)}")
+    return float(ratio.view(-1)[worst]), msg
+
+
 TIMING_LIB = None          # tools/fconv_phases.py: the instrumented build of unet_fused.hip (libsf_fused_timing.so)
 
 
@@ -53,8 +208,9 @@ def run_ops(ops, backend):
 
 def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, silu=True, ss=True, accum=False, resid=False,
                   slots=True, pre_gelu=False, ln_bias=False, seed=0, G=8, scale2=2 ** -0.5, tol=4e-3, dbg=None, reps=1, logits=False,
-                  out_gelu=False, pair=False, pipe=False, pool=False, general=False, one_image=False, tw=None, keep_pipe=False):
-    """tw (r06): run the op on k_conv3s with a tw-pixel-wide tile (W = full-width strips): plain output rows, op field i[19] = tw << 2;
+                  out_gelu=False, pair=False, pipe=False, pool=False, general=False, one_image=False, tw=None, keep_pipe=False, name=None):
+    """Returns the whole-tensor relative L2 error; `name` labels the margin line the case prints (and selects NORM_CHECK_ONLY).
+    tw (r06): run the op on k_conv3s with a tw-pixel-wide tile (W = full-width strips): plain output rows, op field i[19] = tw << 2;
     keep_pipe: the same op with i[19] bit 1 set = the general pipelined kernel."""
     dev = "cpu" if backend == "emu" else "cuda:0"
     d = lambda t: None if t is None else t.to(dev)
@@ -68,16 +224,29 @@ def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, 
         ws = rn(groups, M, npad) * 0.5
         bias1, r1 = rn(C1), rn(M, C1)
         x1 = ws[:, :, :C1].sum(0) + bias1 + r1
+        x1_64 = ws[:, :, :C1].double().sum(0) + bias1.double() + r1.double()
+        dx1 = (groups + 1) * U24 * (ws[:, :, :C1].double().abs().sum(0) + bias1.double().abs() + r1.double().abs())
         s1 = dict(p=d(torch.full((M, C1), float("nan"))), a=d(ws), b=d(bias1), r=d(r1), mode=1, groups=groups, npad=npad)
     elif lazy == 2:
         hh, gate, r1 = rn(M, C1), torch.sigmoid(rn(B, C1)), rn(M, C1)
         x1 = hh * gate.repeat_interleave(HW, 0) + r1
+        x1_64 = hh.double() * gate.double().repeat_interleave(HW, 0) + r1.double()
+        dx1 = 2 * U24 * ((hh.double() * gate.double().repeat_interleave(HW, 0)).abs() + r1.double().abs())
         s1 = dict(p=d(torch.full((M, C1), float("nan"))), a=d(hh), b=d(gate), r=d(r1), mode=2, groups=0, npad=0)
     else:
         x1 = rn(M, C1) * 1.5 + 0.3
+        x1_64, dx1 = x1.double(), torch.zeros(M, C1, dtype=torch.float64)
         s1 = dict(p=d(x1.clone()), a=None, b=None, r=None, mode=0, groups=0, npad=0)
     x2 = rn(M, C2) if C2 else None
     xc = torch.cat([x1, x2 * scale2], 1) if C2 else x1
+    dt = opnd_dtype(backend)
+    sc2_32 = float(torch.tensor(scale2, dtype=torch.float32))                  # the op carries scale2 as a float
+    eps32 = float(torch.tensor(1e-5, dtype=torch.float32))
+    # source 2 as the kernel sees it: without a norm it is ONE fp32 product, rounded to the operand type (bit for bit reproducible); under a
+    # norm the scale may be folded into the slope (fused_conv3s.h), which is one of the N_AFF roundings
+    x2_64 = ((x2 * torch.tensor(sc2_32)).double() if norm == NONE else x2.double() * sc2_32) if C2 else None
+    xc64 = torch.cat([x1_64, x2_64], 1) if C2 else x1_64
+    dxc = torch.cat([dx1, torch.zeros(M, C2, dtype=torch.float64)], 1) if C2 else dx1
     # ---- reference
     gamma, beta = rn(C) * 0.5 + 1, rn(C) * 0.2
     ssv = rn(B, 2 * C) * 0.3 if (ss and norm in (GN_SELF, GN_SLOTS)) else None
@@ -95,14 +264,15 @@ def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, 
         y = F.silu(y)
     w = rn(Cout, C, k, k) / (C * k * k) ** 0.5
     bias = rn(Cout)
-    ref = to_rows(F.conv2d(bf(y), bf(w), None, padding=k // 2))
+    rd = lambda t: t.to(dt).float()                       # operand rounding of the build under test (bf16, or IEEE half for the _f16 library)
+    ref = to_rows(F.conv2d(rd(y), rd(w), None, padding=k // 2))
     # ---- op
     ldc, co_off = (Cout, 0) if (pool or tw is not None) else (Cout + 32, 16)     # epilogue pooling / k_conv3s want the bare conv output
     out0 = rn(M, ldc)
     out = d(out0.clone())
     res = rn(M, ldc) if resid else None
     res_d = d(res)
-    wp = d(fused.pack_conv_weights(w))
+    wp = d(fused.pack_conv_weights(w, dt))
     wsl = d(torch.full((S, M, (Cout + 15) // 16 * 16), float("nan"))) if S > 1 else None
     slots_out = d(torch.full((M // 16, ldc // 16, 2), float("nan"))) if (slots and S == 1 and Cout % 16 == 0) else None
     sl1 = d(slots_of(x1, M, C1)) if norm == GN_SLOTS else None
@@ -115,7 +285,7 @@ def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, 
     lpart = d(torch.full((S * n_frags, M), float("nan"))) if logits else None
     if pool:          # GlobalContext pooling in the epilogue: w_eff[tap][channel] = sum_n wk[n] * W[n][channel][tap], k-step order, bf16
         assert pipe and not logits and k == 3
-        weff = torch.einsum("n,ncyx->yxc", wk, bf(w)).reshape(-1).to(torch.bfloat16).contiguous()
+        weff = torch.einsum("n,ncyx->yxc", wk, rd(w)).reshape(-1).to(dt).contiguous()
         wk_d = d(weff)
         lpart = d(torch.full((M // 16 * Cout + M // 16 * 2,), float("nan")))
     op = fused.mkop(OP_FCONV, (1 if silu else 0) | (2 if pre_gelu else 0) | (4 if accum else 0) | (8 if out_gelu else 0) | (32 if pipe else 0)
@@ -125,12 +295,24 @@ def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, 
                     + ((1,) if one_image else ((((0 if tw == W else tw) << 2) | (2 if keep_pipe else 0),) if tw is not None else ())),      # i[19] bit 0: one image per workgroup (k_conv4_gn) where k_conv4_gn_mb would take the op; bit 1 / bits 2..: k_conv3s
                     f=(1e-5, 1.0, scale2))
     ops = [op]
+    # ---- float64 reference with the kernel's rounding points, and its per-element bound
+    stats = None
+    if norm == GN_SLOTS:               # the statistics the kernel is handed: its fp32 producer slots (source 2: scaled by scale2, scale2^2)
+        assert (C // G) % 16 == 0
+        sl_all = sl1.cpu().double() if not C2 else torch.cat([sl1.cpu().double(), sl2.cpu().double() * torch.tensor([sc2_32, sc2_32 * sc2_32], dtype=torch.float64)], 1)
+        stats = sl_all.view(B, HW // 16, G, C // G // 16, 2).sum((1, 3))
+    s64, ds64 = staged_reference64(xc64, dxc, B, HW, norm, G, gamma, beta if (norm != LN or ln_bias) else None, ssv, silu, eps32, stats, pre_gelu)
+    conv64, bound, amb_share = conv_reference64(s64, ds64, w, dt, B, H, W, S)
     if pair:          # conv1 || res_conv in one launch (k_conv_fused_pair): a 1x1 conv of the RAW concat next to the normalised 3x3 one
         w2 = rn(Cout, C, 1, 1) / C ** 0.5
         bias2 = rn(Cout)
-        ref2 = to_rows(F.conv2d(bf(nhwc(xc, B, H, W)), bf(w2), None)) + bias2
+        ref2 = to_rows(F.conv2d(rd(nhwc(xc, B, H, W)), rd(w2), None)) + bias2
+        xr64 = torch.cat([x1_64, (x2 * torch.tensor(sc2_32)).double()], 1) if C2 else x1_64       # raw operand: reproducible bit for bit unless lazy
+        conv2_64, bound2, _ = conv_reference64(xr64, dxc, w2, dt, B, H, W)
+        want2_64 = conv2_64 + bias2.double()
+        bound2 = bound2 + 2 * U24 * (conv2_64.abs() + bias2.double().abs())
         out2 = d(torch.full((M, Cout), float("nan")))
-        wp2, bias2_d = d(fused.pack_conv_weights(w2)), d(bias2)
+        wp2, bias2_d = d(fused.pack_conv_weights(w2, dt)), d(bias2)
         op.flags |= 16
         ops.append(fused.mkop(OP_FCONV, 0,
                               p=(s1["p"] if not lazy else None, s1["a"], s1["b"], s1["r"], None, x2_d, None, wp2, bias2_d, out2, None, None, None,
@@ -163,6 +345,33 @@ def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, 
         assert torch.equal(out[:, :co_off], out0[:, :co_off]) and torch.equal(out[:, co_off + Cout:], out0[:, co_off + Cout:])
     assert torch.isfinite(got).all()
     e = rel(got, want)
+    # the float64 counterpart of `want` and the epilogue's share of the bound: every fp32 add rounds its own result, which is at most the sum
+    # of the magnitudes of what has been added; at most two adds follow the K-slice reduction in any case (bias, and residual or accumulate)
+    want64, parts = conv64, conv64.abs()
+    if S == 1:
+        for t in (bias, res[:, co_off:co_off + Cout] if resid else None, out0[:, co_off:co_off + Cout] if accum else None):
+            if t is not None:
+                want64, parts = want64 + t.double(), parts + t.double().abs()
+    bound = bound + 2 * U24 * parts
+    if out_gelu:                                         # derivation (c): slope <= 1.13, evaluation error < 8 u |v|
+        bound = 1.13 * bound + 8 * U24 * want64.abs()
+        want64 = _gelu64(want64)
+        bound = bound + U24 * want64.abs()
+    rms = float(want64.pow(2).mean().sqrt())
+    med = float(bound.median()) / rms
+    worst, fails = float("nan"), []
+    if name not in NORM_CHECK_ONLY:
+        worst, msg = check_elements("conv", got, want64, bound, Cout, B, H, W, WM, WN, tw)
+        fails.append(msg)
+        if pair:
+            w2_, msg = check_elements("paired res_conv", out2.cpu(), want2_64, bound2, Cout, B, H, W, WM, WN, tw)
+            worst = max(worst, w2_)
+            fails.append(msg)
+    print(f"margin {backend} {name}: rel-L2 {e:.2e} worst err/bound {worst:.3f} ambiguous {amb_share:.4f} median bound/rms {med:.2e}")
+    # conditions on the reference alone: the allowance cannot grow quietly
+    assert amb_share <= AMB_SHARE_MAX, f"ambiguous share {amb_share:.3g} of the operand: change the case's seed"
+    assert norm not in (GN_SELF, GN_SLOTS) or med <= BOUND_MEDIAN_MAX, f"median bound / rms {med:.3g}"
+    assert not any(fails), "; ".join(m for m in fails if m)
     assert e < tol, f"conv mismatch rel {e}"
     if lazy:
         assert torch.allclose(s1["p"].cpu(), x1, atol=1e-5), "lazy source not materialised correctly"
@@ -188,6 +397,16 @@ def run_conv_case(backend, B, H, W, C1, C2, Cout, k, norm, WM, WN, S=1, lazy=0, 
         if tw is not None and tw != W:                   # 2-D tiles: a fragment holds a 16-pixel patch, not 16 consecutive pixels; consumers sum per image
             sl, got_sl = sl.view(B, HW // 16, Cout // 16, 2).sum(1), got_sl.reshape(B, HW // 16, Cout // 16, 2).sum(1)
         assert torch.allclose(got_sl, sl, rtol=1e-4, atol=2e-3 * (1 if tw is None or tw == W else HW // 16) ** 0.5), "output slots wrong"
+        # derived: float64 slot sums of the kernel's OWN output; a slot is the sum of 256 fp32 values (and of their fma'd squares) in some
+        # order: at most 256 roundings on sum |v| / sum v^2.  (Asserted next to the allclose above until it has held on the GPU.)
+        o64 = out[:, co_off:co_off + Cout].double().contiguous()
+        sl64, sla = slots_of(o64, M, Cout), slots_of(o64.abs(), M, Cout)
+        g64 = slots_out.cpu()[:, co_off // 16:co_off // 16 + Cout // 16].double()
+        if tw is not None and tw != W:
+            sl64, sla, g64 = (t.reshape(B, HW // 16, Cout // 16, 2).sum(1) for t in (sl64, sla, g64))
+        sl_bound = 256 * U24 * torch.stack([sla[..., 0], sl64[..., 1]], -1)
+        nbad = int(((g64 - sl64).abs() > sl_bound).sum())
+        assert nbad == 0, f"output slots: {nbad} outside 256 fp32 roundings, worst err / bound {float(((g64 - sl64).abs() / sl_bound).max()):.3g}"
     return e
 
 

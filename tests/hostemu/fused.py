@@ -57,8 +57,8 @@ def mkop(type_, flags=0, p=(), i=(), f=()):
     return o
 
 
-def pack_conv_weights(w):
-    """[Cout, Cin, kh, kw] fp32 -> MFMA fragment order bf16 (as int16 storage), the layout of sf_conv_pack_weights:
+def pack_conv_weights(w, dt=torch.bfloat16):
+    """[Cout, Cin, kh, kw] fp32 -> MFMA fragment order in the operand type dt (16-bit storage), the layout of sf_conv_pack_weights:
     [n_frag][tap * Cin/32 + cc][lane][8] with element (lane, j) = W[n_frag*16 + (lane & 15)][tap][cc*32 + 8*(lane >> 4) + j]."""
     co, ci, kh, kw = w.shape
     assert ci % 32 == 0
@@ -67,4 +67,4 @@ def pack_conv_weights(w):
     wp[:co] = w.reshape(co, ci, taps)
     # [nf, n16, cc, kb, j, tap] -> [nf, tap, cc, kb, n16, j]
     x = wp.reshape(nfr, 16, cch, 4, 8, taps).permute(0, 5, 2, 3, 1, 4).contiguous()
-    return x.to(torch.bfloat16).reshape(-1)
+    return x.to(dt).reshape(-1)

@@ -1,6 +1,9 @@
 """GPU parity of the fused UNet ops through the C ABI (sf_plan_run): the cases of tests/fused_cases.py -- the small ones
-the CPU-thread emulator also runs, and the UNet's own layer shapes -- against a torch fp32 reference on bf16-rounded
-operands (tolerance 4e-3 relative L2: same operand rounding, different summation order)."""
+the CPU-thread emulator also runs, and the UNet's own layer shapes.  The conv cases carry two checks (tests/fused_cases.py):
+every output element against a float64 reference that rounds where the kernel rounds, within a bound derived from the
+kernel's roundings (operands next to a rounding tie, fp32 accumulation depth, epilogue adds), and the whole tensor
+against a torch fp32 reference on operand-rounded inputs (4e-3 relative L2).  Each case prints its margins
+(profiles/fused_conv_parity_margins.log holds those of the last recorded run)."""
 import pytest
 
 import fused_cases as fc
@@ -11,7 +14,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(fc.CONV_CASES) + sorted(fc.CONV_CASES_FULL))
 def test_fused_conv_on_gpu(name):
     kw = fc.CONV_CASES.get(name) or fc.CONV_CASES_FULL[name]
-    e = fc.run_conv_case("gpu", **kw)
+    e = fc.run_conv_case("gpu", name=name, **kw)
     print(f"{name}: rel {e:.2e}")
 
 

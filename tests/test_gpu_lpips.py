@@ -61,6 +61,28 @@ def test_lpips_distance_and_gradient(B, R, operand):
     assert float(z.detach().abs().max()) < 1e-6 and torch.isfinite(q.grad).all()
 
 
+def test_lpips_distance_is_reproducible_bit_for_bit():
+    """The distance is a sum over up to 256 workgroups of each of the five heads.  They meet in a fixed-point integer, so the order in
+    which they arrive cannot show: 20 evaluations of one pair at 256^2 (the benchmark's size) give one bit pattern, and so does a second
+    module.  (An fp32 atomic in that place let the last bits of the distance -- and of the distillation loss built on it -- vary from run to
+    run: tests/test_gpu_bench_multirank.py::test_dump_outputs_of_the_last_timed_step.)"""
+    from sparsefusion_amd.lpips import LPIPS
+    sd = lpips_ref.init_state(seed=0)
+    g = torch.Generator().manual_seed(11)
+    base = torch.rand(2, 3, 256, 256, generator=g)
+    pred = (base + 0.15 * torch.randn(2, 3, 256, 256, generator=g)).clamp(0, 1).to(DEV)
+    target = base.to(DEV)
+    seen = set()
+    for _ in range(2):
+        net = LPIPS(net='vgg')
+        net.load_state_dict(sd, strict=True)
+        net = net.to(DEV)
+        with torch.no_grad():
+            for _ in range(10):
+                seen.add(tuple(net(pred, target, normalize=True).flatten().cpu().view(torch.int32).tolist()))
+    assert len(seen) == 1, seen
+
+
 def test_lpips_gradient_error_is_operand_rounding_and_where_it_comes_from():
     """The gradient bound of the test above (8e-2 against the fp32 oracle, measured 5-6e-2) is the loosest number of the suite.
     This test (a) localises it -- one feature tap at a time (the other four lin layers zeroed on both sides): the error grows with

@@ -267,6 +267,26 @@ def test_ragged_batches_agree_with_the_one_image_plan(B):
     assert worst < TOL_REL
 
 
+@pytest.mark.parametrize("B", [9, 17])
+def test_ragged_batches_match_oracle(B):
+    """The test above compares the HIP path with itself: a fault that the batch plan and the one-image plan share would pass it.  The two
+    batches with the most ragged tails (B = 9: 1.125 tiles of the 4x4 level; B = 17: one map past the 256-row and 4096-row thresholds), same
+    inputs, against the fp32 oracle with the bounds of test_large_batch_default_plans_match_oracle: overall and for the worst image."""
+    name = "canonical"
+    sd = state(name)
+    net = _unet(name, sd)
+    g = torch.Generator().manual_seed(700 + B)
+    x, cond = torch.randn(B, 4, 32, 32, generator=g), torch.randn(B, 256, 32, 32, generator=g)
+    ls = unet_ref.log_snr(torch.rand(B, generator=g) * 0.98 + 0.01)
+    with torch.no_grad():
+        y_ref = unet_ref.unet_forward(sd, x, ls, cond)
+    y = net.forward_with_cond_scale(x.to(DEV), ls.to(DEV), cond_images=cond.to(DEV)).cpu()
+    r, c = rel_err(y, y_ref), cosine(y, y_ref)
+    worst = max(rel_err(y[b:b + 1], y_ref[b:b + 1]) for b in range(B))
+    print(f"B={B}: rel L2 vs oracle {r:.3e} cosine {c:.6f}; worst image {worst:.3e}")
+    assert torch.isfinite(y).all() and r < TOL_REL and c > TOL_COS and worst < TOL_REL
+
+
 def test_plms_batch8_trajectory_matches_oracle_sampler():
     """51-eval PLMS trajectory at B = 8 (the per-GPU batch of the N = 4 scaling line; first batch on the hybrid plan) against the fp32
     oracle sampler (oracle/unet_ref.plms_sample, pinned to the reference's PLMSSampler by tests/test_oracle_unet.py) with shared noise
