@@ -106,11 +106,16 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
 // x*(scale+1)+shift, SiLU, -> bf16 NHWC; optional raw bf16 copy of the concat.
 //   p[0] src1 f32 [B,HW,C1], p[1] src2 f32 [B,HW,C2] or NULL, p[2] gamma [C], p[3] beta [C],
 //   p[4] scale_shift f32 (row b at p[4] + b*ss_stride: scale[C] then shift[C]) or NULL,
-//   p[5] out bf16 [B,HW,C], p[6] raw bf16 [B,HW,C] or NULL, p[7] stats f64 [B*8][2], zeroed by the caller
-//   i = B, HW, C1, C2, ss_stride, lazy mode, groups, npad, G (0 = 8 groups) ; f = eps, src2_scale ; flags: 1 = no SiLU
-//   p[8..10] lazy source operands of src1 (see LazySrc): k_gn_stats materialises src1 into p[0] while reading it
-// Two launches so that a B=1 eval still fills the chip: k_gn_stats (grid B*8*slices; per-block fp32 partial
-// sums, combined in f64 with one L2 atomic pair per block) and k_gn_apply (pure elementwise).
+//   p[5] out bf16 [B,HW,C], p[6] raw bf16 [B,HW,C] or NULL, p[7] stats f64 [B*G][2] (sum, sum of squares), zeroed by the caller
+//   i = B, HW, C1, C2, ss_stride, lazy mode, groups, npad, G (0 = 8 groups) ; f = eps, src2_scale
+//   flags: 1 = no SiLU, 2 = p[7] already holds the statistics (OP_GN_FINALIZE over a conv epilogue's partial sums; plain single source
+//          only), 4 = always the two-launch form, 8 = k_gn_one wherever a group's slab fits it
+//   p[8..10] lazy source operands of src1 (see LazySrc): the statistics pass (k_gn_stats or k_gn_one) materialises src1 into p[0] while reading it
+// Two launches so that a B=1 eval still fills the chip: k_gn_stats (grid B*G*slices; per-block fp32 partial
+// sums, combined in f64 with one L2 atomic pair per block; k_gn_stats_px for narrow groups) and k_gn_apply (pure elementwise).
+// p[7] after the op: the two-launch form leaves the (sum, sum of squares) of every (image, group) there; k_gn_one keeps its sums in the
+// workgroup and does NOT touch p[7].  Nothing reads p[7] after its own OP_GN_ACT (the planner allocates one buffer per op:
+// unet.py gn_act), and tests/test_gpu_norm_ops.py pins both behaviours.
 // ---------------------------------------------------------------------------------------------
 #define GN_CHUNKS_PER_BLOCK 2048     // float4 chunks per stats workgroup (256 threads x 8)
 
@@ -772,9 +777,14 @@ static int run_gn(const sf_op& op, hipStream_t st) {
   LazySrc lz;
   if (int rc = lazy_from_op(op, 5, B * HW, lz)) return rc;
   const int c4 = C / 4;
-  // r06: one launch for statistics + normalisation when B * G workgroups are a fair share of the chip and a group's slab fits the registers of its
-  // workgroup (the large-batch UNet plans: G = 8, B >= 32; flag 4 = the two-launch form, flag 8 = this form at any B, for comparison)
-  if (!(op.flags & (2 | 4)) && (B * G >= 256 || (B * G >= 64 && (long)B * HW * C <= (1L << 19)) || (op.flags & 8)) && chunks <= 1024 * 16) {      // (... or a tensor of <= 2 MB on >= 64 workgroups: the 4x4 level of B >= 8)      // (measured: B = 32 eval 4.81 -> 4.66 ms; at 64 / 128 workgroups the pair wins: B = 8 2.46 vs 2.54 ms, B = 16 3.65 vs 3.68; flag 8 forces k_gn_one)
+  // r06: one launch for statistics + normalisation when a group's slab fits the registers of its workgroup (<= 1024 * 16 float4) and either
+  //   * B * G >= 256 workgroups (G = 8: the UNet plans from B = 32 on; G = 32: every VAE GroupNorm without epilogue statistics from B = 8 on), or
+  //   * B * G >= 64 workgroups and the tensor has at most 2^19 elements (2 MB: the 4x4 level of the B >= 8 UNet plans).
+  // Flag 4 = the two-launch form, flag 8 = this form at any B, flag 2 (ready-made statistics) never takes it.  Measured on G = 8 only: B = 32 eval
+  // 4.81 -> 4.66 ms; on the larger tensors of 64 / 128 workgroups the pair wins (B = 8 2.46 vs 2.54 ms, B = 16 3.65 vs 3.68), hence the size limit
+  // of the second condition.  G = 32 takes the same rule unmeasured; its results are checked per element on every instantiation
+  // (tests/test_gpu_norm_ops.py).
+  if (!(op.flags & (2 | 4)) && (B * G >= 256 || (B * G >= 64 && (long)B * HW * C <= (1L << 19)) || (op.flags & 8)) && chunks <= 1024 * 16) {
     float* s1 = (float*)op.p[0];
     const float *s2 = (const float*)op.p[1], *ga = (const float*)op.p[2], *be = (const float*)op.p[3], *ssp = (const float*)op.p[4];
     sf_opnd *o = (sf_opnd*)op.p[5], *rw = (sf_opnd*)op.p[6];

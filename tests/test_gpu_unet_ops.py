@@ -438,6 +438,10 @@ def test_layernorm(R, C, gelu, bias, f32, res):
         assert torch.allclose(out.cpu(), ref, rtol=1e-5, atol=2e-5)
     else:
         assert torch.allclose(out.float().cpu(), ref, rtol=1.2e-2, atol=1e-2)
+        # per element: float64 LayerNorm, half a bf16 ulp + the derived fp32 uncertainty (tests/norm_cases.py (b)), mismatch share capped
+        import norm_cases as nc
+        want, delta = nc.layernorm_ref64(x, gain, b if bias else None, 1e-5, pre_gelu=bool(int(gelu) & 1))
+        nc.check_bf16(f"layernorm R {R} C {C} gelu {int(gelu)}", out.cpu(), want, delta, old=(1.2e-2, 1e-2))
 
 
 @pytest.mark.parametrize("M,N,K,in_silu,act", [(1, 1024, 17, False, 1), (2, 5000, 1024, True, 0), (8, 128, 256, False, 0),
@@ -508,6 +512,10 @@ def test_attention_core_self_and_cross():
     att = torch.einsum('bhid,bjd->bhij', qh, k).softmax(-1)
     ref = torch.einsum('bhij,bjd->bhid', att, v).permute(0, 2, 1, 3).reshape(B * 16, 512)
     assert torch.allclose(out.float().cpu(), ref, rtol=1.2e-2, atol=1e-2)
+    import norm_cases as nc
+    as_heads = lambda t: t.view(B, 16, heads, dh).permute(0, 2, 1, 3)          # [B * 16, 512] -> [B, heads, 16, dh]
+    want, delta = nc.attn16_ref64(as_heads(q), k[:, None].expand(B, heads, -1, dh), v[:, None].expand(B, heads, -1, dh), dh ** -0.5)
+    nc.check_bf16("attention core self", as_heads(out.cpu()), want, delta, old=(1.2e-2, 1e-2))
     # cross attention: per-head k/v from 2 context tokens + shared null
     kvc = torch.randn(B * 2, 1024, generator=g).to(DEV)
     _run([_op(5, 0, p=(qd, out, nd, nd.data_ptr() + 256, kvc, kvc.data_ptr() + 2048, None, None),
@@ -519,6 +527,8 @@ def test_attention_core_self_and_cross():
     att = torch.einsum('bhid,bhjd->bhij', qh, kk).softmax(-1)
     ref = torch.einsum('bhij,bhjd->bhid', att, vv).permute(0, 2, 1, 3).reshape(B * 16, 512)
     assert torch.allclose(out.float().cpu(), ref, rtol=1.2e-2, atol=1e-2)
+    want, delta = nc.attn16_ref64(as_heads(q), kk, vv, dh ** -0.5)
+    nc.check_bf16("attention core cross", as_heads(out.cpu()), want, delta, old=(1.2e-2, 1e-2))
 
 
 def test_gca_pool_gate_and_layout_ops():

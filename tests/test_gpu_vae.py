@@ -69,3 +69,46 @@ def test_vae_rejects_unsupported():
     net = AutoencoderKL(ddconfig=ddconfig(CONFIGS["small"]))
     with pytest.raises((RuntimeError, AssertionError)):
         net.encode(torch.zeros(1, 3, 32, 32))                # CPU tensor: no fallback
+
+
+@pytest.mark.parametrize("B", [8, 9])
+def test_small_large_batch_matches_oracle_with_and_without_gn_one(B):
+    """The B >= 8 plans take other kernels than the golden batch and B = 3 (k_gn_one from B * 32 >= 256 workgroups on, other conv
+    tilings): the small configuration at B = 8 and B = 9 against the oracle on fresh weights, and the same inputs with
+    `gn_one = False` (k_gn_stats(_px) + k_gn_apply everywhere, op flag 4): both within REL of the oracle and of each other."""
+    from sparsefusion_amd import unet as unet_mod
+    from sparsefusion_amd.vae import AutoencoderKL
+    cfg = CONFIGS["small"]
+    sd = state("small", seed=5)
+    img, z = inputs(cfg, B, seed=40 + B)
+    with torch.no_grad():
+        lat_ref, dec_ref = vae_ref.encode_mode(sd, cfg, img), vae_ref.decode(sd, cfg, z)
+    got = {}
+    for gn_one in (True, False):
+        net = AutoencoderKL(ddconfig=ddconfig(cfg), embed_dim=cfg["embed_dim"])
+        net.load_state_dict(sd)
+        net.gn_one = gn_one                                       # read when a plan is built
+        net = net.cuda()
+        lat, dec = net.encode(img.cuda()).mode().cpu(), net.decode(z.cuda()).cpu()
+        gns = [o for p in net._plans.values() for o in p.ops if o.type == unet_mod.OP_GN_ACT]
+        assert gns and all(bool(o.flags & 4) != gn_one for o in gns)
+        print(f"small B {B} gn_one {gn_one}: latents rel {rel_err(lat, lat_ref):.2e} cos {cosine(lat, lat_ref):.6f}; "
+              f"decoded rel {rel_err(dec, dec_ref):.2e} cos {cosine(dec, dec_ref):.6f}")
+        assert torch.isfinite(lat).all() and torch.isfinite(dec).all()
+        assert rel_err(lat, lat_ref) < REL and cosine(lat, lat_ref) > COS
+        assert rel_err(dec, dec_ref) < REL and cosine(dec, dec_ref) > COS
+        got[gn_one] = (lat, dec)
+    assert rel_err(got[False][0], got[True][0]) < REL and rel_err(got[False][1], got[True][1]) < REL
+
+
+def test_canonical_decode_at_b8_matches_oracle():
+    """The canonical decoder at B = 8 against the CPU oracle (about 2 s per image on 8 threads) on fresh inputs: the conv tilings of a
+    large batch, every GroupNorm on the statistics its producing conv left (conv flag 128 -> OP_GN_FINALIZE -> flag 2), eight per-sample
+    attention chains."""
+    net, cfg = _vae("canonical")
+    _, z = inputs(cfg, 8, seed=77)
+    with torch.no_grad():
+        dec_ref = vae_ref.decode(state("canonical"), cfg, z)
+    dec = net.decode(z.cuda()).cpu()
+    print(f"canonical B 8: decoded rel {rel_err(dec, dec_ref):.2e} cos {cosine(dec, dec_ref):.6f}")
+    assert torch.isfinite(dec).all() and rel_err(dec, dec_ref) < REL and cosine(dec, dec_ref) > COS

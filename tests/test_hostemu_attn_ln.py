@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import norm_cases as nc
 from hostemu import fused
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostemu")
@@ -47,6 +48,8 @@ def test_layernorm_kernel(R, Cc, gelu, bias, resid, out_f32):
         assert torch.allclose(out, want, rtol=1e-5, atol=2e-5), float((out - want).abs().max())
     else:
         assert torch.allclose(out.float(), want, rtol=8e-3, atol=8e-3)          # bf16 output
+        w64, delta = nc.layernorm_ref64(x, gain, b, 1e-5, pre_gelu=bool(int(gelu) & 1))          # per element: tests/norm_cases.py (b)
+        nc.check_bf16(f"emu layernorm R {R} C {Cc} gelu {int(gelu)}", out, w64, delta, old=(8e-3, 8e-3))
 
 
 @pytest.mark.parametrize("out_f32", [True, False])
@@ -72,3 +75,6 @@ def test_attention_core_kernel(out_f32):
         assert torch.allclose(out, want, rtol=1e-5, atol=1e-5), float((out - want).abs().max())
     else:
         assert torch.allclose(out.float(), want, rtol=8e-3, atol=8e-3)
+        as_heads = lambda t: t.view(B, 16, heads, dh).permute(0, 2, 1, 3)
+        w64, delta = nc.attn16_ref64(as_heads(q), k[:, None].expand(B, heads, -1, dh), v[:, None].expand(B, heads, -1, dh), dh ** -0.5)
+        nc.check_bf16("emu attention core", as_heads(out), w64, delta, old=(8e-3, 8e-3))

@@ -483,3 +483,88 @@ def test_unet_plans_of_every_batch_regime_pass_the_op_audit():
         plan = _Plan(net, B, CPU, (s.zero.off, s.misc.off + s.ws_bytes + s.ws2_bytes + 512, s.ws_bytes, s.ws2_bytes)).build()
         assert _audit(plan.ops, f"unet B={B}", sized=True) >= 91
         assert plan.ws_owner is None or plan.ws_owner.lazy is None
+
+
+def test_gn_geometry_restates_run_gn():
+    """tests/norm_cases.py::gn_geometry is the dispatch rule of run_gn (csrc/unet_ops.hip) in Python: it supplies the per-thread chunk count
+    n_t of the statistics bound and names the kernel a GPU case is written for.  Checked here on the shapes of the issue that asked for the
+    GPU cases (chunks = HW * (C / G) / 4 picks the k_gn_one instantiation), on the slab / slice rules, and against the rule's own text."""
+    import norm_cases as nc
+    one = lambda B, HW, C, fl=0: (lambda g: (g["kernel"], g.get("NT"), g.get("NCH"), g["chunks"]))(nc.gn_geometry(B, HW, C, 0, 32, fl))
+    assert one(8, 256, 256) == ("k_gn_one", 256, 2, 512) and one(8, 256, 512) == ("k_gn_one", 256, 4, 1024)
+    assert one(8, 1024, 256) == ("k_gn_one", 256, 8, 2048) and one(8, 1024, 512) == ("k_gn_one", 256, 16, 4096)
+    assert one(8, 4096, 256) == ("k_gn_one", 1024, 8, 8192) and one(8, 4096, 512) == ("k_gn_one", 1024, 16, 16384)
+    assert one(8, 36, 128) == ("k_gn_one", 256, 2, 36)
+    assert one(8, 16384, 128) == ("k_gn_one", 1024, 16, 16384)
+    assert one(8, 16384, 256)[0] == one(8, 16384, 256, 8)[0] == "k_gn_stats_px"            # 32768 chunks: the pair, forced or not
+    assert one(8, 256, 256, 4)[0] == "k_gn_stats_px" and one(1, 256, 256, 8)[0] == "k_gn_one" and one(1, 256, 256)[0] == "k_gn_stats_px"
+    assert one(2, 256, 1024)[0] == "k_gn_one" and one(2, 320, 1024)[0] == "k_gn_stats" and one(1, 256, 1024)[0] == "k_gn_stats"      # the second rule
+    px = lambda B, HW, C: nc.gn_geometry(B, HW, C, 0, 32, 0)
+    assert px(1, 64, 128)["slabs"] == 1 and px(1, 65536, 128)["slabs"] == 512 and px(1, 65536, 512)["slabs"] == 1024
+    assert px(1, 65536, 512)["n_t"] == 32 and px(1, 1000, 128) == dict(kernel="k_gn_stats_px", slabs=7, ppi=8, n_t=18, chunks=1000)
+    assert nc.gn_geometry(2, 1024, 384, 0, 32)["kernel"] == "k_gn_stats"                      # 256 % (C / 4) != 0
+    assert nc.gn_geometry(2, 1024, 256, 256, 32)["kernel"] == "k_gn_stats"                    # two sources
+    assert nc.gn_geometry(1, 1024, 256, 0, 32, 0, lazy=1) == dict(kernel="k_gn_stats", slices=8, n_t=1, chunks=2048)       # a lazy split-K source: 256 chunks per workgroup
+    assert nc.gn_geometry(1, 256, 384, 128, 32)["slices"] == 4 and nc.gn_geometry(1, 16384, 384, 0, 32)["slices"] == 24   # small-map rule; 2048 chunks per slice
+    assert nc.gn_geometry(2, 256, 128, 0, 32, 2)["kernel"] == "ready"
+    # the constants of the rule, from its text
+    src = open(os.path.join(ROOT, "sparsefusion_amd", "csrc", "unet_ops.hip")).read()
+    body = src[src.index("static int run_gn("):src.index("static int run_ln(")]
+    for token in ("B * G >= 256", "B * G >= 64", "(1L << 19)", "chunks <= 1024 * 16", "C / G <= 16 && c4 <= 256 && 256 % c4 == 0", "HW / (ppi * 16)",
+                  "slabs > 1024 ? 1024", "lz.mode == 1 ? 256 : GN_CHUNKS_PER_BLOCK", "128 / (B * G)"):
+        assert token in body, token
+    assert "#define GN_CHUNKS_PER_BLOCK 2048" in src
+    assert [tuple(map(int, m)) for m in re.findall(r"SF_GN_ONE\((\d+), (\d+)\);", body)] == [(256, 2), (256, 4), (256, 8), (256, 16), (1024, 8), (1024, 16)]
+    # every GPU case names the branch gn_geometry gives it
+    import test_gpu_norm_ops as T
+    seen = set()
+    for table in (T.GN_ONE_CASES, T.GN_PX_CASES, T.GN_STATS_CASES, T.GN_LAZY_CASES, T.GN_EDGE_CASES):
+        for name, kw in table.items():
+            for fl in kw.get("flags", (0, 4, 8)):
+                g = nc.gn_geometry(kw["B"], kw["HW"], kw["C1"], kw.get("C2", 0), kw.get("G", 32), fl, kw.get("lazy", 0))
+                e = kw["expect"][fl]
+                assert (g["kernel"], g.get("NT"), g.get("NCH")) == e if isinstance(e, tuple) else g["kernel"] == e, (name, fl, g)
+                seen.add((g["kernel"], g.get("NT"), g.get("NCH")))
+                assert kw["B"] * kw["HW"] * (kw["C1"] + kw.get("C2", 0)) * 4 <= 256 << 20, name      # no single device tensor above 256 MB
+    assert {(k, nt, nch) for k, nt, nch in seen if k == "k_gn_one"} == {("k_gn_one", nt, nch) for nt, nch in ((256, 2), (256, 4), (256, 8), (256, 16), (1024, 8), (1024, 16))}
+    assert {"k_gn_stats_px", "k_gn_stats"} <= {k for k, _, _ in seen}
+
+
+@pytest.mark.parametrize("name,B,HW,C,G,eps,silu,kind", [("g32_silu", 2, 1024, 512, 32, 1e-6, True, "normal"), ("g32_no_silu", 2, 1024, 512, 32, 1e-6, False, "normal"),
+                                                         ("variance_near_eps", 2, 1024, 512, 32, 1e-6, True, "tiny_var"), ("mean_8_sigma", 2, 1024, 512, 32, 1e-6, True, "mean8"),
+                                                         ("g8", 2, 256, 512, 8, 1e-5, True, "normal")])
+def test_norm_reference_alone_stays_under_the_mismatch_cap(name, B, HW, C, G, eps, silu, kind):
+    """The per-element GroupNorm bound and the mismatch cap of tests/norm_cases.py, on a CPU restatement of the kernel chain in fp32
+    (gn_chain_f32: the summation order of k_gn_stats, k_gn_apply's expression unfused): the float64 reference ALONE, with no kernel in
+    the loop, leaves the share of elements whose bf16 differs under the cap and every element inside half_ulp + delta -- so a GPU case
+    that exceeds either says something about the kernel.  Inputs: the generators of the GPU cases."""
+    import norm_cases as nc
+    import test_gpu_norm_ops as T
+    g = torch.Generator().manual_seed(B + HW + C)
+    x = T._source(kind, B, HW, C, C // G, g)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.2 * torch.randn(C, generator=g)
+    ss_all = torch.randn(B, 2 * C, generator=g) * 0.3
+    ss = (ss_all[:, :C], ss_all[:, C:])
+    got = nc.gn_chain_f32(x, G, gamma, beta, eps, ss=ss, silu=silu, n_t=8)
+    want, delta, _, _ = nc.gn_act_ref64(x.double(), None, 1.0, G, gamma, beta, eps, (8 + 8, 4 * 8 + 6), ss=ss, silu=silu)
+    fig = nc.check_bf16(f"reference alone {name}", got, want, delta, old=(1.2e-2, 1e-2))
+    assert 0 < fig["mismatch"] <= nc.MISMATCH_MAX and fig["worst"] <= 1
+    # ... and the bound is not slack enough to hide an eps of 1e-5 where 1e-6 was asked, at a variance near eps
+    if kind == "tiny_var":
+        wrong = nc.gn_chain_f32(x, G, gamma, beta, 1e-5, ss=ss, silu=silu, n_t=8)
+        with pytest.raises(AssertionError):
+            nc.check_bf16("reference alone, eps 1e-5 for 1e-6", wrong, want, delta, log=False)
+
+
+@pytest.mark.parametrize("N", [32, 200, 1024])
+def test_softmax_reference_alone_stays_under_the_mismatch_cap(N):
+    """The same for the softmax rows: an fp32 restatement (k_softmax_rows' expression) against softmax_ref64 on the GPU case's rows."""
+    import norm_cases as nc
+    import test_gpu_norm_ops as T
+    x = T._softmax_rows_input(N, torch.Generator().manual_seed(N))
+    t = x * torch.tensor(0.125)
+    e = torch.exp(t - t.max(1, keepdim=True).values)
+    got = (e * (1.0 / e.sum(1, keepdim=True))).to(torch.bfloat16)
+    want, delta = nc.softmax_ref64(x, 0.125)
+    fig = nc.check_bf16(f"reference alone softmax N {N}", got, want, delta)
+    assert fig["worst"] <= 1
