@@ -23,7 +23,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .unet import OP_ELTWISE, OP_MEMSET, Unet, _Node, _Plan, _T
+from .plan import OP_ELTWISE, OP_MEMSET, Plan, PlanOwner, _T
+from .unet import _Node
 
 OP_POOL, OP_EFT = 11, 13
 RAY_DIM, DEPTH_DIM = 78, 13                     # HarmonicEmbedding(6): (2*6+1) * {6, 1}
@@ -73,7 +74,7 @@ def _i64(v):
     return (v & 0xffffffff) - (1 << 32) if (v & 0xffffffff) >= (1 << 31) else (v & 0xffffffff), v >> 32
 
 
-class _EftPlan(_Plan):
+class _EftPlan(Plan):
     def eft_op(self, sub, p, ints, f=()):
         self.op(OP_EFT, sub, p=p, i=ints, f=f)
 
@@ -87,7 +88,7 @@ class _EftPlan(_Plan):
         xin = self.f32(NC * HW, 32, HW)
         self.op(OP_ELTWISE, 2, p=(0, self.x_in.ptr, 0, xin.ptr), i=(NC, HW, 0, 3, 32))
         H = R // 2
-        x0 = self.zf32(NC * H * H, 64, H * H)
+        x0 = self.f32(NC * H * H, 64, H * H)
         self.conv(xin, True, R, R, e + ".conv1.weight", e + ".conv1.fbias", x0, 64, 0, 64, 7, 2, 3, relu=True)
         Hp = (H - 1) // 2 + 1
         x = self.f32(NC * Hp * Hp, 64, Hp * Hp)
@@ -100,11 +101,11 @@ class _EftPlan(_Plan):
                 Ho = (Hc + 2 - 3) // s + 1
                 idt = x
                 if (p + ".downsample.0.weight") in self.w:
-                    idt = self.zf32(NC * Ho * Ho, cout, Ho * Ho)
+                    idt = self.f32(NC * Ho * Ho, cout, Ho * Ho)
                     self.conv(x, True, Hc, Hc, p + ".downsample.0.weight", p + ".downsample.0.fbias", idt, cout, 0, cout, 1, s, 0)
-                h = self.zf32(NC * Ho * Ho, cout, Ho * Ho)
+                h = self.f32(NC * Ho * Ho, cout, Ho * Ho)
                 self.conv(x, True, Hc, Hc, p + ".conv1.weight", p + ".conv1.fbias", h, cout, 0, cout, 3, s, 1, relu=True)
-                y = self.zf32(NC * Ho * Ho, cout, Ho * Ho)
+                y = self.f32(NC * Ho * Ho, cout, Ho * Ho)
                 self.conv(h, True, Ho, Ho, p + ".conv2.weight", p + ".conv2.fbias", y, cout, 0, cout, 3, 1, 1, resid=idt, relu=True)
                 x, Hc = y, Ho
             latents.append((x, Hc))
@@ -126,13 +127,13 @@ class _EftPlan(_Plan):
         """r04: where the producer left an operand-type twin of x (a LayerNorm, a ReLU linear, the attention core), the linear reads
         that -- half the A bytes, and the LDS-DMA kernel (k_conv_glds) instead of the register-staged k_conv_lds: the 48 K = 256
         linears of the three transformers were 7.5 ms of a 13.8 ms feature render.  Same operand values (the fp32 path rounds on load)."""
-        tw = x.twin if getattr(self.u, "linear_twin", True) else None
+        tw = x.twin if self.u.linear_twin else None
         self.conv(tw if tw is not None else x, tw is None, 1, M, wname, bname, out, cout, 0, cout, 1, batch=1, resid=resid, relu=(act == 1),
                   gelu=(act == 2), twin=twin)
 
     def encoder_layer(self, p, x, M, S, stride, gmul):
-        tw_ok = getattr(self.u, "linear_twin", True) and M >= 1024
-        qkv = self.zf32(M, 768)
+        tw_ok = self.u.linear_twin and M >= 1024
+        qkv = self.f32(M, 768)
         self.linear(x, M, p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", qkv, 768)
         if tw_ok:                                                 # the attention core writes the operand type directly (no fp32 copy)
             att = _T(0, M, 256)
@@ -141,22 +142,22 @@ class _EftPlan(_Plan):
         else:
             att = self.f32(M, 256)
             self.eft_op(3, (qkv.ptr, 0, 0, att.ptr), _i64(M // S) + (S,) + _i64(stride) + _i64(gmul), (1.0 / math.sqrt(256.0),))
-        y = self.zf32(M, 256)
+        y = self.f32(M, 256)
         self.linear(att, M, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", y, 256, resid=x)
         x1 = self.f32(M, 256)
         self.ln(y, p + ".norm1.weight", p + ".norm1.bias", x1, 256, M, out_f32=True, twin=self.bf16(M, 256) if tw_ok else None)
-        h = self.zf32(M, 256)
+        h = self.f32(M, 256)
         self.linear(x1, M, p + ".linear1.weight", p + ".linear1.bias", h, 256, act=1, twin=self.bf16(M, 256) if tw_ok else None)
-        y2 = self.zf32(M, 256)
+        y2 = self.f32(M, 256)
         self.linear(h, M, p + ".linear2.weight", p + ".linear2.bias", y2, 256, resid=x1)
         x2 = self.f32(M, 256)
         self.ln(y2, p + ".norm2.weight", p + ".norm2.bias", x2, 256, M, out_f32=True, twin=self.bf16(M, 256) if tw_ok else None)
         return x2
 
     def transformer(self, t, w_in, K, M, S, stride, gmul):
-        x = self.zf32(M, 256)
+        x = self.f32(M, 256)
         self.linear(_T(w_in.ptr, M, K), M, t + ".pre.0.weight", t + ".pre.0.bias", x, 256, act=2,
-                    twin=self.bf16(M, 256) if (getattr(self.u, "linear_twin", True) and M >= 1024) else None)
+                    twin=self.bf16(M, 256) if (self.u.linear_twin and M >= 1024) else None)
         for i in range(4):
             x = self.encoder_layer(f"{t}.encoder.layers.{i}", x, M, S, stride, gmul)
         return x
@@ -207,7 +208,7 @@ class _EftPlan(_Plan):
         return self
 
 
-class EpipolarFeatureTransformer(nn.Module):
+class EpipolarFeatureTransformer(PlanOwner, nn.Module):
     def __init__(self, use_r=True, n_harmonic_functions=6, conv_dims=(32,), return_features=False, encoder='lite',
                  remove_unused_layers=True, in_dim=3, out_dim=3, out_sigmoid=True, omega0=1.0, verbose=False):
         super().__init__()
@@ -221,11 +222,9 @@ class EpipolarFeatureTransformer(nn.Module):
         for name, shape in eft_param_spec(remove_unused_layers):
             self._add(name, shape, g)
         self.input_bbox = self.input_cameras = self.input_images = self.encoder_latent = None
-        self.conv_waves_target, self.lazy_consumers, self.ss_total, self.lds_conv_min_blocks = 1024, 0, 0, 96
+        self.lds_conv_min_blocks = 96
         self.linear_twin = True             # r04: transformer linears read operand-type twins their producers leave (False: fp32 reads; tests compare)
         self._pack_cache, self._plans, self._enc = None, {}, None
-
-    conv_tiling = Unet.conv_tiling
 
     def _add(self, dotted, shape, g):
         parts = dotted.split(".")

@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .unet import OP_CONV, OP_ELTWISE, OP_MEMSET, Unet, _Plan, _register, _T
+from .plan import OP_ELTWISE, OP_MEMSET, Plan, PlanOwner, _T
+from .unet import _register
 
 OP_POOL, OP_LPIPS = 11, 12
 SHIFT = (-.030, -.088, -.188)
@@ -39,7 +40,7 @@ def lpips_param_spec():
     return spec
 
 
-class _LpipsPlan(_Plan):
+class _LpipsPlan(Plan):
     """kind 'fwd': features + distance for V pairs; kind 'bwd': d distance / d pred, reading the forward plan's buffers."""
 
     def __init__(self, mod, V, R, device, sizing=None, fwd=None):
@@ -64,13 +65,13 @@ class _LpipsPlan(_Plan):
                 self.op(OP_POOL, 0, p=(h.ptr, 0, 0, y.ptr), i=(B, H, H, h.C))
                 self.pool_in[ci] = (h, H)                          # conv ci reads the pooled copy of h
                 h, H, cur = y, H // 2, sl
-            y = self.zf32(B * H * H, cout, H * H)
+            y = self.f32(B * H * H, cout, H * H)
             name = f"net.slice{sl}.{idx}"
             # a conv followed by a conv of the same slice also leaves its ReLU output in operand type (r03): the next conv then runs on
             # k_conv3_halo (csrc/conv_halo.h) instead of converting fp32 in registers on k_conv_lds; same rounding, same operands
-            nxt = ci + 1 < len(VGG_CONVS) and VGG_CONVS[ci + 1][0] == sl and getattr(self.u, "conv_twin", True)
+            nxt = ci + 1 < len(VGG_CONVS) and VGG_CONVS[ci + 1][0] == sl and self.u.conv_twin
             tw = self.bf16(B * H * H, cout, H * H) if nxt else None
-            src = h.twin if getattr(self.u, "conv_twin", True) else None
+            src = h.twin if self.u.conv_twin else None
             self.conv(src if src is not None else h, src is None, H, H, name + ".weight", name + ".bias", y, cout, 0, cout, 3, 1, 1,
                       relu=True, twin=tw)
             self.conv_in.append(h)
@@ -110,7 +111,7 @@ class _LpipsPlan(_Plan):
             gz = self.bf16(V * H * H, cout, H * H)                 # ReLU backward: dz = g * (y > 0), bf16 operand of the conv
             self.op(OP_ELTWISE, 7, p=(g.ptr, y.ptr, 0, gz.ptr), i=(V * H * H * cout,))
             cpad = 32 if cin == 3 else cin
-            gx = self.zf32(V * H * H, cpad, H * H)                 # gradient w.r.t. this conv's input
+            gx = self.f32(V * H * H, cpad, H * H)                 # gradient w.r.t. this conv's input
             name = f"net.slice{sl}.{idx}"
             self.conv(gz, False, H, H, name + ".weight.T", None, gx, cpad, 0, cpad, 3, 1, 1)
             g = gx
@@ -158,7 +159,7 @@ class _LpipsFn(torch.autograd.Function):
         return None, out.view(ctx.shape), None
 
 
-class LPIPS(nn.Module):
+class LPIPS(PlanOwner, nn.Module):
     """lpips.LPIPS(net='vgg', verbose=False) surface: forward(in0, in1, normalize=False) -> [B,1,1,1]."""
 
     def __init__(self, net='vgg', verbose=False, **unsupported):
@@ -174,9 +175,6 @@ class LPIPS(nn.Module):
             else:
                 t = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * 9))
             _register(self, name, nn.Parameter(t, requires_grad=False))
-        self.conv_waves_target = 1024
-        self.lazy_consumers = 0
-        self.ss_total = 0
         self.lds_conv_min_blocks = 96
         self.conv_twin = True             # conv -> conv links of a VGG slice in operand type (r03); False = fp32 reads
         self._pack_cache, self._plans, self._serial = None, {}, 0
@@ -194,8 +192,6 @@ class LPIPS(nn.Module):
         # the `lpips` package ships pretrained VGG16 + learned lin heads; this module starts from a seeded random init and has
         # no network access: until load_state_dict() brings real weights the distance is NOT the LPIPS metric
         self._weights_loaded = False
-
-    conv_tiling = Unet.conv_tiling
 
     def invalidate(self):
         self._pack_cache, self._plans = None, {}

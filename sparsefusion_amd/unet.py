@@ -18,22 +18,22 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .plan import (FNORM_ATTN, FNORM_GN_SELF, FNORM_GN_SLOTS, FNORM_LN, FNORM_NONE, LDS_MAX, OP_ATTN, OP_CONV, OP_ELTWISE, OP_FCONV, OP_GCA,   # noqa: F401
+                   OP_GCA_POOL, OP_GEMV, OP_GN_ACT, OP_GN_FINALIZE, OP_INITX, OP_LN, OP_MEMSET, OP_SLOTS, OP_SPLITK_REDUCE, OP_TIME_EMB,
+                   SKIP_SCALE, Plan, PlanOwner, _T)       # (re-exported: tests and tools import the codes from here)
 
-OP_CONV, OP_GN_ACT, OP_LN, OP_GEMV, OP_ATTN, OP_GCA_POOL, OP_ELTWISE, OP_MEMSET, OP_TIME_EMB, OP_SPLITK_REDUCE = range(1, 11)
-OP_FCONV, OP_SLOTS, OP_GCA, OP_INITX, OP_GN_FINALIZE = 14, 15, 16, 17, 18
 # (WM, WN, norm of conv1) for which k_conv_fused_pair is instantiated (csrc/fused_host.h SF_FCONV_PAIR_VARIANTS); FNORM_GN_SELF = 1, _SLOTS = 2
 PAIR_TILES = {(1, 1, 1), (1, 1, 2), (1, 2, 2), (2, 2, 2), (4, 2, 2)}
 # (WM, WN, (TR + 2) * W / 8) for which k_conv_fused_pipe is instantiated (SF_FCONV_PIPE_VARIANTS)
+PIPE_TILES = {(1, 1, 4), (1, 2, 4), (1, 1, 6), (1, 2, 6), (2, 1, 6), (2, 2, 6), (2, 1, 8), (2, 2, 8), (2, 1, 12), (2, 2, 12), (4, 1, 16), (4, 2, 16)}
 # (log2 H, C = Cout, log2 tile width, WM, WN) of k_conv3s (csrc/fused_host.h SF_CONV3S_VARIANTS; tests/test_plans_cpu.py compares the two tables)
 CONV3S_VARIANTS = {(5, 256, 5, 2, 2), (5, 256, 3, 2, 2), (4, 256, 4, 1, 1), (4, 256, 2, 1, 1), (4, 512, 4, 1, 2), (4, 512, 2, 1, 2),
                    (3, 512, 3, 1, 1), (3, 1024, 3, 1, 1), (5, 256, 5, 4, 2), (5, 256, 3, 4, 2),
                    (4, 256, 2, 2, 1), (4, 256, 2, 2, 2), (4, 512, 2, 2, 2), (3, 512, 3, 2, 1), (3, 1024, 3, 2, 1), (3, 1024, 3, 2, 2)}
 # (log2 H, C1, C2, Cout, log2 tile width, WM, WN) of k_conv3s_rc (SF_CONV3S_RC_VARIANTS): conv1 on a concat + the block's res_conv in one set of workgroups
 CONV3S_RC_VARIANTS = {(5, 256, 256, 256, 3, 2, 2), (4, 512, 256, 512, 2, 1, 2), (3, 1024, 512, 1024, 3, 1, 1)}
-PIPE_TILES = {(1, 1, 4), (1, 2, 4), (1, 1, 6), (1, 2, 6), (2, 1, 6), (2, 2, 6), (2, 1, 8), (2, 2, 8), (2, 1, 12), (2, 2, 12), (4, 1, 16), (4, 2, 16)}
-FNORM_NONE, FNORM_GN_SELF, FNORM_GN_SLOTS, FNORM_LN, FNORM_ATTN = range(5)      # csrc/fused_kernels.h
 ATTN_LDS_BYTES = 8 * 16 * 36 * 4 + 2 * 8 * 4 * 68 * 4      # SF_ATTN_LDS_BYTES: scratch of the attention prologue (FNORM_ATTN)
-# Measured (WM, WN, split-K groups) of implicit-GEMM launches where the cost model of Unet.conv_tiling picks a slower tile
+# Measured (WM, WN, split-K groups) of implicit-GEMM launches where the cost model of PlanOwner.conv_tiling picks a slower tile
 # (tools/tile_sweep.py on MI355X, whole-eval time, r03: B = 1 eval 1.3246 -> 1.3004 ms): key = (m_frags, n_frags, KS, pixshuf).
 # The up-sampling 1x1 convs (PixelShuffle epilogue, no split-K) want ONE 16-row fragment per wave: a (4, 1) tile left 128
 # workgroups pulling 256 KB of fp32 activations each.
@@ -45,8 +45,46 @@ TILE_PICKS = {(4, 32, 128, False): (1, 2, 8),      # Downsample 16x16 -> 8x8, 25
               (64, 16, 128, False): (2, 4, 4), (16, 32, 128, False): (1, 4, 4), (4, 64, 256, False): (1, 2, 4),
               (4, 64, 288, False): (1, 4, 4), (4, 256, 32, True): (1, 2, 1), (16, 128, 32, True): (1, 4, 1),
               (64, 64, 16, True): (1, 2, 1)}
-LDS_MAX = 163840
-SKIP_SCALE = 2 ** -0.5            # scale_skip_connection (imagen_pytorch.py:1283)
+
+# Planner switches of the UNet, in the order Unet.__init__ sets them: (name, default, meaning).  Plain instance attributes (since r04 -- the
+# SF_* environment switches of the r01-r03 A/B runs are retired); an A/B run sets them by name (Unet.set_switches: tools/unet_time.py and
+# tools/graph_ablate.py through SF_UNET_ATTRS), tests/test_gpu_unet.py::test_plan_switches_match_oracle covers them.
+SWITCHES = (
+    ("conv_waves_target", 1024, "waves wanted per conv launch (4 per CU) before split-K stops"),
+    ("lds_conv_min_blocks", 96, "use k_conv_lds when a layer has at least this many 128 x 128 output tiles"),
+    ("lds_mid_min_rows", 128, "r06: convs of >= this many rows that have too few 128-row tiles for lds_conv_min_blocks run on the LDS-tiled kernels with split-K groups (Plan.conv); 0 = off"),
+    ("merged_down_conv4", True, "r06: the merged 3x3 + 1x1 conv of the last Downsample on k_conv4_gn<64, 0, false> at B = 1; False: k_conv_igemm"),
+    ("rc_small_tiles", 32, "r06: bit mask of map sides (32 | 16 | 8) whose B >= 2 (conv1 || res_conv) pairs keep the B = 1 tile of k_conv3s_rc (32: B = 2 eval 1.155 -> 1.139 ms, B = 4 1.562 -> 1.520; 32 | 16: B = 4 1.580, B = 8 2.451 -> 2.550)"),
+    ("gn_one", True, "r06: GroupNorm passes of B >= 32 plans (B * 8 >= 256 workgroups) in one launch (k_gn_one); False: k_gn_stats + k_gn_apply everywhere"),
+    ("lds_mid_min_batch", 8, "... in plans of at least this many images (the B = 1 .. 4 plans keep their measured kernels)"),
+    ("unfused_min_rows_4", 256, "r06: 4x4-level ResnetBlocks with B*16 >= this leave the fused kernels (as unfused_min_rows at 32x32 / 16x16; measured: B = 8 loses 0.12 ms, B = 16 gains 0.22, B = 32 0.49); 0 = never"),
+    ("unfused_min_rows_8", 1024, "... 8x8 level (k_conv3_halo_sm; measured: B = 8 loses 0.14 ms, B = 16 gains 0.04, B = 32 0.56)"),
+    ("unfused_lin_min_rows", 256, "r06: attention / feed-forward linears of the 4x4 level with >= this many token rows leave the fused kernels (measured: B = 16 3.683 -> 3.670 ms, B = 32 4.664 -> 4.472)"),
+    ("unfused_min_rows_16", 4096, "r06: the 16x16 level's own threshold (0 = unfused_min_rows; measured with k_gemm_rows_ks / the r06 plans: B = 16 3.641 -> 3.313 ms; 2048 rows lose: B = 8 2.454 -> 2.512)"),
+    ("unfused_min_rows_32", 0, "... 32x32 level (4096 rows lose: B = 4 1.575 -> 1.686 ms)"),
+    ("unfused_min_rows", 8192, "ResnetBlocks with B*H*W >= this at the 32x32 / 16x16 levels leave the fused kernels (_Plan.resnet; measured r03: B = 8 eval 3.33 -> 2.96 ms, B = 32 11.5 -> 7.8 ms, B = 4 unchanged)"),
+    ("lazy_consumers", 3, "bit 0: split-K reductions, bit 1: gated residuals are materialised by their first consumer"),
+    ("fused", True, "GroupNorm inside the conv launches (k_conv_fused) wherever the layer fits; False = the first-round plan"),
+    ("pair_res_conv", True, "conv1 || res_conv of a ResnetBlock in one launch"),
+    ("res_conv_beside_pool", True, "4x4 gca blocks: the res_conv shares the GlobalContext pooling launch instead"),
+    ("initx_direct", True, "latent half of the init conv as one direct-convolution launch"),
+    ("big_tile_min_batch", 2, "batch from which the 8x8 / 16x16 / 32x32 maps use 32- / 32- / 64-pixel tiles (r03: B = 2 eval 1.70 -> 1.50 ms, B = 4 2.62 -> 2.02, B = 32 16.4 -> 11.5; at B = 1 they would leave half the CUs idle; 999 = never)"),
+    ("gca_epilogue_pool", True, "GlobalContext pooling in conv2's epilogue (False = k_gca_pool launch)"),
+    ("fconv_pipe", True, "slot-GroupNorm 3x3 convs on k_conv_fused_pipe (staging || matrix work)"),
+    ("producer_slots", True, "r04: k_init_x / the Upsample epilogue leave their consumers' statistics slots, the final conv's split-K reduction writes NCHW (False: the r03 k_slots / k_unpack_out launches; parity tests)"),
+    ("attn_in_out_proj", True, "the 16-token attention core in the prologue of its output projection (False: k_attn16 launch; parity tests)"),
+    ("ln_wave", True, "r05: LayerNorm of <= 256 rows of 512 | 1024 | 2048 channels on k_layernorm_wave (False: op flag 4 = k_layernorm)"),
+    ("gate_t", True, "r05: GlobalContext gate with a compile-time hidden width (k_gca_gate_t; False: k_gca_gate)"),
+    ("conv4_reduce_min_batch", 4, "r05: from this batch on a 4x4 split-K conv1 is reduced by its own launch instead of by conv2's gather (0 = never)"),
+    ("conv4_mb", True, "r05: even B: the 4x4 GroupNorm-self convs run 2 | 4 images per workgroup (k_conv4_gn_mb; False = op field i[19] bit 0)"),
+    ("conv4_slices_max_batch", 4, "r05: up to this batch the 4x4 GroupNorm-self convs keep 4 input-channel slices (= k_conv4_gn's geometry); 0 = the workgroup-count rule alone"),
+    ("conv3s", True, "r06: the recurring single-source slot-GroupNorm 3x3 convs on k_conv3s (compile-time geometry, csrc/fused_conv3s.h); False: op field i[19] bit 1 = k_conv_fused_pipe"),
+    ("conv3s_tw32", 8, "r06: tile width of k_conv3s's 2-D pixel tiles per map size (0 = full-width strips)"),
+    ("conv3s_tw16", 4, "... 16x16 maps"),
+    ("conv3s_tw8", 0, "... 8x8 maps"),
+    ("conv4", True, "r05: the 4x4 level's GroupNorm-self 3x3 convs on k_conv4_gn (csrc/fused_conv4.h); False: op flag 128 = k_conv_fused (parity tests)"),
+    ("use_hip_graph", True, "replay one captured hipGraph per eval instead of ~370 host launches"),
+)
 
 
 def init_x_weight_table(ws, dtype=torch.bfloat16):
@@ -188,276 +226,19 @@ def _register(root, dotted, tensor):
 
 
 # ------------------------------------------------------------------------------------------------
-# plan building
+# plan building (the generic emitters: plan.py)
 # ------------------------------------------------------------------------------------------------
-class _Arena:
-    """Bump allocator over one device tensor.  `base=None` = sizing pass (offsets only)."""
-
-    def __init__(self, nbytes=None, device=None):
-        self.off = 0
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
-
-    def alloc(self, nbytes):
-        nbytes = (nbytes + 255) // 256 * 256
-        off = self.off
-        self.off += nbytes
-        return (self.buf.data_ptr() + off) if self.buf is not None else (1 << 20) + off
-
-
-class _T:
-    """A planned activation: device pointer + logical shape [B, HW, C] (NHWC) or [rows, C]."""
-    __slots__ = ("ptr", "rows", "C", "HW", "lazy", "slots", "writer", "twin")
-
-    def __init__(self, ptr, rows, C, HW=None):
-        self.ptr, self.rows, self.C, self.HW = ptr, rows, C, HW
-        # lazy: None, or how the first consumer must materialise the tensor (csrc/unet_ops.hip LazySrc):
-        #   ("splitk", ws, bias, resid, groups, npad, ws index)   or   ("gate", h, gate, res)
-        self.lazy = None
-        # slots: device pointer of the [rows/16][C/16][2] (sum, sum of squares) table of the materialised values that a
-        # GroupNorm-fused conv reads its statistics from (csrc/fused_kernels.h), or None
-        self.slots = None
-        self.twin = None            # operand-type copy [rows][C] written by the producing conv's epilogue (_Plan.conv twin=), or None
-        # writer: the OP_CONV op (k_conv_lds) that wrote the whole tensor last, or None (experimental GroupNorm-partials epilogue)
-        self.writer = None
-
-
-class _Plan:
-    def __init__(self, unet, B, device, sizing=None):
-        self.u, self.B, self.dev = unet, B, device
-        self.ops = []
-        self.graph = None
-        if sizing is None:
-            self.zero, self.misc = _Arena(), _Arena()
-        else:
-            self.zero, self.misc = _Arena(sizing[0], device), _Arena(sizing[1], device)
-        self.w = unet._packed(device)
-        self.written = set()                 # (ptr, channel offset) of conv outputs that already hold data
-        # two split-K workspaces (max demand over the ops that use each; ops run serially): a fused conv reads its input's
-        # slabs from one while it writes its own partial tiles to the other
-        self.ws_need = [0, 0]
-        self.ws_ptrs = [self.misc.alloc(sizing[2]) if sizing is not None else 0,
-                        self.misc.alloc(sizing[3]) if sizing is not None and len(sizing) > 3 and sizing[3] else 0]
-        self.ws_owners = [None, None]        # tensors whose un-reduced split-K partials currently live in each workspace
-
-    @property
-    def ws_bytes(self):
-        return self.ws_need[0]
-
-    @property
-    def ws2_bytes(self):
-        return self.ws_need[1]
-
-    @property
-    def ws_owner(self):
-        return next((o for o in self.ws_owners if o is not None and o.lazy is not None), None)
-
-    def acquire_ws(self, nbytes, avoid=()):
-        """Index of a workspace the op being emitted may overwrite: a free one if possible, never one that holds the
-        partials of a tensor in `avoid` (an input of that op); a workspace owned by another tensor is reduced first."""
-        for i in sorted(range(2), key=lambda j: (self.ws_owners[j] is not None and self.ws_owners[j].lazy is not None, j)):
-            o = self.ws_owners[i]
-            if o is not None and o.lazy is not None:
-                if any(o is t for t in avoid):
-                    continue
-                self.need(o)
-            self.ws_need[i] = max(self.ws_need[i], nbytes)
-            self.ws_owners[i] = None
-            return i
-        raise AssertionError("no split-K workspace available")
-
-    # -------- allocation helpers
-    def zf32(self, rows, C, HW=None):        # conv outputs: first writer stores, later writers accumulate
-        return self.f32(rows, C, HW)
-
-    def f32(self, rows, C, HW=None):
-        return _T(self.misc.alloc(rows * C * 4), rows, C, HW)
-
-    def bf16(self, rows, C, HW=None):
-        return _T(self.misc.alloc(rows * C * 2), rows, C, HW)
-
-    def op(self, type_, flags=0, p=(), i=(), f=()):
-        o = _lib.SfOp()
-        o.type, o.flags = type_, flags
-        for k, v in enumerate(p):
-            o.p[k] = v if v else None
-        for k, v in enumerate(i):
-            o.i[k] = int(v)
-        for k, v in enumerate(f):
-            o.f[k] = float(v)
-        self.ops.append(o)
-
-    def wptr(self, name):
-        return self.w[name].data_ptr()
-
-    # -------- lazy tensors: the first consumer materialises them (saves one dependent launch each)
-    def need(self, t):
-        """Emit the stand-alone materialisation of a lazy tensor for consumers that cannot do it themselves."""
-        if t is None or t.lazy is None:
-            return t
-        lz, t.lazy = t.lazy, None
-        if lz[0] == "splitk":
-            _, ws, bias, resid, groups, npad, wi = lz
-            self.op(OP_SPLITK_REDUCE, 0, p=(ws, bias, resid, t.ptr), i=(t.rows, t.C, npad, groups))
-            self.ws_owners[wi] = None
-        else:
-            _, h, gate, res = lz
-            self.op(OP_ELTWISE, 1, p=(h, gate, res, t.ptr), i=(self.B, t.HW, t.C))
-        return t
-
-    def take_lazy(self, t, allow):
-        """(p[8..10], (mode, groups, npad)) for a consumer that materialises `t` itself; clears the lazy state."""
-        if t.lazy is None or t.lazy[0] not in allow:
-            self.need(t)
-            return (0, 0, 0), (0, 0, 0)
-        lz, t.lazy = t.lazy, None
-        if lz[0] == "splitk":
-            self.ws_owners[lz[6]] = None
-            return (lz[1], lz[2], lz[3]), (1, lz[4], lz[5])
-        return (lz[1], lz[2], lz[3]), (2, 0, 0)
-
-    # -------- op emitters
-    def conv(self, x, x_f32, H, W, wname, bname, out, ldc, co_off, Cout, k, stride=1, pad=0, resid=None, pixshuf=False,
-             defer=False, w_ptr=None, batch=None, out_hw=None, upsampled=False, relu=False, gelu=False, twin=None, want_slots=False,
-             nchw=False, defer_max_groups=8):
-        """One implicit-GEMM launch.  `w_ptr` replaces the named weight by a device-packed B operand (attention),
-        `batch` overrides the plan batch (per-sample GEMMs), `out_hw` the output size (asymmetric padding),
-        `upsampled` makes (H, W) the dims of a nearest-x2 view of the stored [H/2, W/2] input.  `twin`: a dense operand-type
-        [M][Cout] buffer the epilogue of an LDS-tiled kernel also fills (the A operand of a following conv: no fp32 round trip);
-        out.twin is set when the chosen kernel writes it."""
-        B = self.B if batch is None else batch
-        self.need(x)
-        self.need(resid)
-        Ho, Wo = out_hw or ((H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1)
-        M = B * Ho * Wo
-        m_frags, n_frags = (M + 15) // 16, (Cout + 15) // 16
-        KS = k * k * (x.C // 32)
-        WM, WN, groups = self.u.conv_tiling(m_frags, n_frags, KS, pixshuf)
-        accum = (out.ptr, co_off) in self.written
-        self.written.add((out.ptr, co_off))
-        tile = WM * 16 + WN
-        twin_ws = 0
-        # large-M layers (VAE, VGG, B >= 4): the LDS-tiled kernel, 128 pixels x 128 (or 64) channels per workgroup
-        lds_min = getattr(self.u, "lds_conv_min_blocks", 0)
-        mid = getattr(self.u, "lds_mid_min_rows", 0) if B >= getattr(self.u, "lds_mid_min_batch", 8) else 0
-        if lds_min and n_frags >= 4 and (not pixshuf or (mid and M >= mid and Cout % 4 == 0)):
-            bnf = 8 if n_frags > 4 else 4
-            blocks = ((m_frags + 7) // 8) * ((n_frags + bnf - 1) // bnf)
-            if bnf == 8 and blocks < 256:                     # fewer tiles than CUs: halve the channel tile instead of idling CUs
-                bnf, blocks = 4, ((m_frags + 7) // 8) * ((n_frags + 3) // 4)
-            # 3x3 layers k_conv3_halo takes (csrc/conv_halo.h) beat the weight-streaming kernel from 64 tiles on (measured 21 vs 29 us
-            # on the 32x32 512->512 layer); everything else needs lds_min tiles
-            halo = (k == 3 and stride == 1 and pad == 1 and not x_f32 and x.C % 64 == 0 and W % 16 == 0 and H % 8 == 0 and M % 128 == 0
-                    and Cout % 4 == 0 and ldc % 4 == 0 and co_off % 4 == 0 and (Ho, Wo) == (H, W) and not pixshuf)
-            if blocks >= (min(lds_min, 64) if halo else lds_min) and not pixshuf:
-                tile, groups = 256 + bnf, 1
-                if twin is not None and ldc == Cout and co_off == 0:
-                    twin_ws = twin.ptr
-            elif mid and M >= mid:
-                # r06: M of a few hundred rows (the 4x4 level of B >= 8, the Upsample 1x1 convs): still 128-row MFMA tiles out of LDS, the
-                # workgroups that are missing come from split-K groups over the stage range (k_conv_lds / k_conv_glds; not under the
-                # pixel shuffle, whose epilogue writes the output itself) -- every weight byte is still fetched by ONE workgroup per pixel tile
-                glds_ok = not x_f32 and x.C % 64 == 0 and Cout % 4 == 0 and ldc % 4 == 0 and co_off % 4 == 0
-                stages = KS // 2 if glds_ok else (KS + 1) // 2
-                g = 1 if pixshuf else max(1, min(256 // blocks, stages // 4, 16))
-                if glds_ok and k == 3 and stride == 1 and pad == 1 and H == W and H in (4, 8) and not pixshuf:
-                    # whole 4x4 / 8x8 maps: k_conv3_halo_sm (csrc/conv_halo_small.h) splits K by 64-channel chunk, two chunks per group at least
-                    # (the frames of the second are staged under the taps of the first)
-                    g = max(1, min(256 // blocks, x.C // 128, 16))
-                tile, groups = 256 + bnf, g
-        ws, wi = 0, 0
-        if groups > 1:
-            wi = self.acquire_ws(groups * M * n_frags * 16 * 4)   # a workspace about to be overwritten is reduced first
-            ws = self.ws_ptrs[wi]
-        elif twin_ws:
-            ws = twin_ws
-        defer = bool(defer and not relu and not gelu and 1 < groups <= defer_max_groups and not accum and not pixshuf and co_off == 0 and ldc == Cout == out.C and M == out.rows
-                     and (self.u.lazy_consumers & 1))
-        bias, res = self.wptr(bname) if bname else 0, resid.ptr if resid else 0
-        # r04: the SiLU + PixelShuffle epilogue of an Upsample also leaves the (sum, sum of squares) slots of its output for the next
-        # GroupNorm-fused conv (was a k_slots launch): one slot per MFMA fragment, filed under the right (image, 16-channel column)
-        slots = 0
-        if want_slots and pixshuf and tile < 256 and (Cout // 4) % 16 == 0 and ldc % 16 == 0 and co_off % 16 == 0 and (Ho * Wo) % 16 == 0 and not accum:
-            slots = self.misc.alloc(4 * M // 16 * (ldc // 16) * 2 * 4)
-        # nchw: the (non-deferred) split-K reduction of this conv writes the plan's NCHW output directly (was k_unpack_out)
-        nchw = bool(nchw and groups > 1 and not defer and not accum and not resid and tile < 256 and co_off == 0 and ldc == Cout)
-        self.op(OP_CONV, (1 if x_f32 else 0) | (2 if pixshuf else 0) | (4 if accum else 0) | (8 if defer else 0) |
-                (16 if upsampled else 0) | (32 if relu else 0) | (64 if gelu else 0) | (256 if nchw else 0),
-                p=(x.ptr, w_ptr if w_ptr is not None else self.wptr(wname), bias, out.ptr, res, ws, 0, slots),
-                i=(B, H, W, x.C, Ho, Wo, Cout, ldc, co_off, k, k, stride, pad, groups, tile))
-        if defer:
-            out.lazy = ("splitk", ws, bias, res, groups, n_frags * 16, wi)
-            self.ws_owners[wi] = out
-        out.slots = slots or None
-        self.last_conv_nchw = nchw
-        out.writer = self.ops[-1] if (tile >= 256 and co_off == 0 and ldc == Cout == out.C and M == out.rows) else None
-        out.twin = twin if (twin is not None and tile >= 256 and groups == 1 and ws == twin.ptr) else None
-        return Ho, Wo
-
-    def gn_act(self, x, skip, gname, ss_ptr, out, raw=None, silu=True, groups=8, eps=1e-5):
-        C1, C2 = x.C, (skip.C if skip else 0)
-        self.need(skip)
-        lp, li = self.take_lazy(x, ("splitk", "gate"))
-        stats = self.zero.alloc(self.B * groups * 2 * 8)     # f64 (sum, sum of squares) per (b, group), zeroed per eval
-        ready = 0
-        wr = x.writer
-        cg = (C1 // groups) if not skip else 0
-        if (getattr(self.u, "gn_epilogue", False) and wr is not None and not (wr.flags & 128) and li[0] == 0 and cg in (4, 8, 16)
-                and x.HW and x.HW % 128 == 0 and x.rows == self.B * x.HW):
-            # (VAE plans; SF_VAE_GN_EPI=0 disables) the producing k_conv_lds leaves per-tile partial sums, k_gn_finalize adds them up,
-            # and the statistics pass over the tensor (k_gn_stats_px) is skipped
-            part = self.misc.alloc(x.rows // 128 * groups * 2 * 8)
-            wr.flags |= 128
-            wr.p[6] = part or None
-            wr.i[15] = cg
-            self.op(OP_GN_FINALIZE, 0, p=(part, stats), i=(self.B, x.HW // 128, groups))
-            ready = 2
-        self.op(OP_GN_ACT, (0 if silu else 1) | ready | (0 if getattr(self.u, "gn_one", True) else 4),      # (flag 4: k_gn_stats + k_gn_apply even where k_gn_one fits)
-                p=(x.ptr, skip.ptr if skip else 0, self.wptr(gname + ".weight"), self.wptr(gname + ".bias"), ss_ptr, out.ptr,
-                   raw.ptr if raw else 0, stats) + lp,
-                i=(self.B, x.HW, C1, C2, getattr(self.u, "tb_stride", 0)) + li + (groups,), f=(eps, SKIP_SCALE))
-
-    def ln(self, x, gname, bname, out, C, rows, eps=1e-5, gelu=False, out_f32=False, resid=None, twin=None):
-        """`twin`: an operand-type [rows][C] buffer that also receives the (fp32-output) result -- the A operand of the next linear
-        (k_layernorm_w256: C = 256, rows >= 1024 only)."""
-        self.need(x)
-        self.need(resid)
-        assert twin is None or (out_f32 and C == 256 and rows >= 1024)
-        self.op(OP_LN, (1 if gelu else 0) | (2 if out_f32 else 0) | (0 if getattr(self.u, "ln_wave", True) else 4),
-                p=(x.ptr, self.wptr(gname), self.wptr(bname) if bname else 0, out.ptr, resid.ptr if resid else 0, twin.ptr if twin else 0),
-                i=(rows, C), f=(eps,))
-        out.twin = twin
-
-    def gemv(self, x_ptr, M, ldx, wname, bname, y_ptr, ldy, N, K, in_silu=False, out_act=0):
-        Kp = (K + 7) // 8 * 8
-        # > 8 rows (a sampler's time table): k_gemm_rows, up to 64 rows per launch 
-        step = 8 if M <= 8 else 64
-        for m0 in range(0, M, step):
-            mm = min(step, M - m0)
-            self.op(OP_GEMV, (1 if in_silu else 0) | (out_act << 1),
-                    p=(x_ptr + m0 * ldx * 4, self.wptr(wname), self.wptr(bname) if bname else 0, y_ptr + m0 * ldy * 4),
-                    i=(mm, N, K, Kp, ldx, ldy))
-
-    def attn(self, q, out, segs, heads, ldq, scale, out_f32=False):
-        p = [q.ptr, out.ptr]
-        i = [self.B, heads, ldq, 0]
-        for s in (segs + [None] * 3)[:3]:
-            if s is None:
-                p += [0, 0]
-                i += [0, 0, 0, 0]
-            else:
-                p += [s[0], s[1]]
-                i += list(s[2:])
-        self.op(OP_ATTN, 1 if out_f32 else 0, p=p, i=i, f=(scale,))
-
+class _Plan(Plan):
+    """The UNet's layer logic on the emitters of plan.Plan."""
 
     # -------- fused GroupNorm / LayerNorm -> conv ops (csrc/fused_kernels.h)
     def fused_geometry(self, H, C, Cout, norm, k):
         """(TR, WM, WN, S) of a k_conv_fused launch on an H x H map, or None when the layer does not fit the kernel."""
         B = self.B
-        if not getattr(self.u, "fused", False) or H not in (4, 8, 16, 32) or C % 32 or Cout % 16:
+        if not self.u.fused or H not in (4, 8, 16, 32) or C % 32 or Cout % 16:
             return None
         TR, WM = {4: (4, 1), 8: (2, 1), 16: (1, 1), 32: (1, 2)}[H]
-        if B >= getattr(self.u, "big_tile_min_batch", 2) and H in (8, 16, 32):
+        if B >= self.u.big_tile_min_batch and H in (8, 16, 32):
             # twice the pixels per workgroup (32 at 8x8 / 16x16, 64 at 32x32) once the batch fills the chip: half the weight
             # re-reads per pixel, a smaller halo share.  conv1 || res_conv of a
             # ResnetBlock share a launch and must agree on the tile: the 1x1 half decides as its 3x3 partner (same C) does.
@@ -473,7 +254,7 @@ class _Plan:
         MT = B * (H // TR)
         h = k // 2
 
-        pipe_ok = (getattr(self.u, "fconv_pipe", False) and norm == FNORM_GN_SLOTS and k == 3 and C % 128 == 0
+        pipe_ok = (self.u.fconv_pipe and norm == FNORM_GN_SLOTS and k == 3 and C % 128 == 0
                    and ((TR + 2) * H) % 8 == 0)
 
         def lds_bytes(S_, WN_):
@@ -499,7 +280,7 @@ class _Plan:
         if not cand:
             return None
         S = next((d for d in cand if MT * n_frags * d >= 256), cand[-1])
-        if ((B <= getattr(self.u, "conv4_slices_max_batch", 4) or (getattr(self.u, "conv4_mb", True) and B % 2 == 0)) and getattr(self.u, "conv4", True)
+        if ((B <= self.u.conv4_slices_max_batch or (self.u.conv4_mb and B % 2 == 0)) and self.u.conv4
                 and norm == FNORM_GN_SELF and H == 4 and k == 3 and C in (1024, 2048) and 4 in cand):
             S = 4               # r05: keep k_conv4_gn's 4-slice geometry where the workgroup count alone would pick fewer slices (B = 2: S = 2, B = 4:
                                 # S = 1, both on the general kernel): B = 2 eval 1.287 -> 1.240 ms, B = 4 1.734 -> 1.730 (profiles/r05_conv4_batch_ab.log);
@@ -594,13 +375,13 @@ class _Plan:
             ap = tuple(sk for sk, *_ in segs)
             ai = (ldq,) + tuple(v for _, _, rows, rs, bs, hs in segs for v in (rows, rs, bs, hs))
             af = tuple((sv - sk) // 4 for sk, sv, *_ in segs) + (scale,)
-        elif norm == FNORM_GN_SELF and not getattr(self.u, "conv4_mb", True):
+        elif norm == FNORM_GN_SELF and not self.u.conv4_mb:
             ai = (1,)                                           # i[19] bit 0: one image per workgroup (k_conv4_gn) where k_conv4_gn_mb would take the op
         elif pipe:
             # r06: the recurring single-source geometries run on k_conv3s (csrc/fused_conv3s.h; the host takes the op when a variant of its
             # shape exists).  i[19] bit 1 keeps the general pipelined kernel, bits 2.. = tile width of a 2-D pixel tile (0 = full-width strips)
-            code = 0 if getattr(self.u, "conv3s", True) else 2
-            tw = getattr(self.u, f"conv3s_tw{H}", 0)
+            code = 0 if self.u.conv3s else 2
+            tw = self.conv3s_tw(H)
             if (code == 0 and tw and tw != H and C2 == 0 and Cout == C1 and ldc == Cout and co_off == 0 and not accum and not out_gelu and not pre_gelu
                     and not pair_first and pair_lazy is None and (logit is None or pool is not None) and bname
                     and (H.bit_length() - 1, C1, tw.bit_length() - 1, WM, WN) in CONV3S_VARIANTS):
@@ -610,7 +391,7 @@ class _Plan:
                 code |= (tw if tw != H else 0) << 2                # the pair runs on k_conv3s_rc (the host checks that the res_conv fits)
             ai = (code,)
         self.op(OP_FCONV, (1 if silu else 0) | (2 if pre_gelu else 0) | (4 if accum else 0) | (8 if out_gelu else 0) | (16 if pair_first else 0)
-                | (32 if pipe else 0) | (64 if pool is not None else 0) | (0 if getattr(self.u, "conv4", True) else 128),
+                | (32 if pipe else 0) | (64 if pool is not None else 0) | (0 if self.u.conv4 else 128),
                 p=(x_ptr, lp[0], lp[1], lp[2], x.slots or 0, skip.ptr if skip else 0, (skip.slots or 0) if skip else 0,
                    self.wptr(wname), 0 if S > 1 else bias, out.ptr, 0 if S > 1 else res, ws, slots_out, gam, bet, ss_ptr, 0,
                    logit[0] if logit else 0, logit[1] if logit else 0) + ap,
@@ -620,7 +401,7 @@ class _Plan:
             out.lazy = ("splitk", ws, bias, res, S, n_frags * 16, wi)
             self.ws_owners[wi] = out
             out.slots = None
-            thr = getattr(self.u, "conv4_reduce_min_batch", 0)
+            thr = self.u.conv4_reduce_min_batch
             if thr and B >= thr and H == 4 and norm == FNORM_GN_SELF and logit is None and not pair_first:
                 self.need(out)      # (a paired conv1 is followed by its res_conv in the SAME launch: no op may stand between them -- resnet_fused reduces after the pair)
                                     # r05: reduce the slabs in their own launch -- the consuming conv's 64 n-tile workgroups then gather one float4 per
@@ -628,10 +409,14 @@ class _Plan:
                                     # B = 32 7.24 -> 6.86 ms (profiles/r05_conv4_mb_ab.log); at B = 1 the extra launch costs more than the gather
         return lp, li
 
+    def conv3s_tw(self, H):
+        """Tile width of k_conv3s's 2-D pixel tiles on an H x H map (H = 8 | 16 | 32; 0 = full-width strips)."""
+        return getattr(self.u, f"conv3s_tw{H}")
+
     def pipe_ok(self, C1, C2, H, geom, norm, k, silu=True):
         """A slot-GroupNorm 3x3 conv with a plain source runs on k_conv_fused_pipe (staging || matrix work) when its tile exists."""
         TR, WM, WN, S = geom
-        return bool(getattr(self.u, "fconv_pipe", False) and norm == FNORM_GN_SLOTS and k == 3 and S == 1 and silu
+        return bool(self.u.fconv_pipe and norm == FNORM_GN_SLOTS and k == 3 and S == 1 and silu
                     and (C1 + C2) % 128 == 0 and C1 % 4 == 0 and ((TR + 2) * H) % 8 == 0 and (WM, WN, (TR + 2) * H // 8) in PIPE_TILES)
 
     def resnet_fused(self, name, x, skip, cout, H, gca=False, cross=False):
@@ -646,28 +431,28 @@ class _Plan:
         gr = self.fused_geometry(H, cin, cout, FNORM_NONE, 1) if cin != cout else g1
         if g1 is None or g2 is None or gr is None or x.C % 32 or rows % 16:
             return None
-        if (B >= 2 and (getattr(self.u, "rc_small_tiles", 0) & H) and cin != cout and skip is not None and getattr(self.u, "conv3s", True)
-                and getattr(self.u, "pair_res_conv", True)):
+        if (B >= 2 and (self.u.rc_small_tiles & H) and cin != cout and skip is not None and self.u.conv3s
+                and self.u.pair_res_conv):
             # r06: a (conv1 on the concat || res_conv) pair of B >= 2 keeps the B = 1 tile where k_conv3s_rc has it: the 32- / 64-pixel tiles of
             # B >= 2 do not fit that kernel's registers, and the general pair kernel they fall back to is slower than more workgroups of the small one
             TR0, WM0 = {8: (2, 1), 16: (1, 1), 32: (1, 2)}[H]
             s1, sr = self._fused_geometry(H, cin, cout, norm, 3, TR0, WM0), self._fused_geometry(H, cin, cout, FNORM_NONE, 1, TR0, WM0)
-            tw = getattr(self.u, f"conv3s_tw{H}", 0) or H
+            tw = self.conv3s_tw(H) or H
             if (s1 is not None and sr is not None and s1[1:3] == sr[1:3] and sr[3] == 1
                     and (H.bit_length() - 1, x.C, skip.C, cout, tw.bit_length() - 1, s1[1], s1[2]) in CONV3S_RC_VARIANTS):
                 g1, gr = s1, sr
         slots = norm == FNORM_GN_SLOTS
-        h = self.zf32(rows, cout, HW)
+        h = self.f32(rows, cout, HW)
         # conv1 and res_conv read the same input and are independent: one launch (k_conv_fused_pair) when their tiles match
-        pair = (cin != cout and getattr(self.u, "pair_res_conv", True) and g1[1:3] == gr[1:3] and gr[3] == 1
+        pair = (cin != cout and self.u.pair_res_conv and g1[1:3] == gr[1:3] and gr[3] == 1
                 and (g1[1], g1[2], norm) in PAIR_TILES)
         # r04, 4x4 level: a gca block's res_conv is only needed by the gate, so it runs beside the 16-workgroup pooling launch
         # (k_gca_pool_rc) on the materialised input instead of as a second round of workgroups re-reducing conv1's lazy source
-        late_rc = (cin != cout and gca and H == 4 and getattr(self.u, "res_conv_beside_pool", True) and gr[1:4] == (1, 1, 1)
+        late_rc = (cin != cout and gca and H == 4 and self.u.res_conv_beside_pool and gr[1:4] == (1, 1, 1)
                    and cout % 64 == 0 and cout <= 2048 and cin <= 4096)    # (LDS: 16 pixels x cin operands beside the pooling's 9 KB)
         # r05: conv1 of the 4x4 level runs on k_conv4_gn where its geometry fits (csrc/fused_conv4.h); the pair kernel is the general one,
         # so such a block emits conv1 and its res_conv as two launches (26.7 us as a pair against ~10 + 9.3 us)
-        conv4_geom = (H == 4 and getattr(self.u, "conv4", True) and g1[1:3] == (1, 1) and g1[3] > 1 and cin // g1[3] in (256, 512)
+        conv4_geom = (H == 4 and self.u.conv4 and g1[1:3] == (1, 1) and g1[3] > 1 and cin // g1[3] in (256, 512)
                       and (cin // 8) * 2 == cin // g1[3])
         pair = pair and not late_rc and not conv4_geom
         lz = self.fconv(x, skip, H, f"{name}.block1.project.weight", f"{name}.block1.project.bias", h, cout, 3, norm, g1,
@@ -675,12 +460,12 @@ class _Plan:
         rc = None
         emit_rc = None
         if cin != cout:                                             # res_conv reads the raw concat (x is materialised by conv1)
-            rc = self.zf32(rows, cout, HW)
+            rc = self.f32(rows, cout, HW)
             emit_rc = lambda first=False: self.fconv(x, skip, H, f"{name}.res_conv.weight", f"{name}.res_conv.bias", rc, cout, 1,
                                                      FNORM_NONE, gr, silu=False, pair_lazy=lz if pair else None, pair_first=first)
             if not late_rc:
                 emit_rc()
-                thr = getattr(self.u, "conv4_reduce_min_batch", 0)
+                thr = self.u.conv4_reduce_min_batch
                 if pair and thr and B >= thr and H == 4 and norm == FNORM_GN_SELF and h.lazy is not None and h.lazy[0] == "splitk":
                     self.need(h)                                        # the own-launch reduction of fconv(), behind the pair
         if cross:
@@ -688,12 +473,12 @@ class _Plan:
         ss_ptr = self.ss.ptr + self.u.ss_offset[name] * 4
         w2, b2, gn2 = f"{name}.block2.project.weight", f"{name}.block2.project.bias", f"{name}.block2.groupnorm"
         res = rc if rc is not None else x
-        out = self.zf32(rows, cout, HW)
+        out = self.f32(rows, cout, HW)
         if not gca:
             self.fconv(h, None, H, w2, b2, out, cout, 3, norm, g2, gname=gn2, ss_ptr=ss_ptr, resid=res, want_slots=slots)
             return out
-        h2 = self.zf32(rows, cout, HW)
-        if (getattr(self.u, "gca_epilogue_pool", True) and cout % 64 == 0 and cout <= 2048 and HW % 16 == 0 and HW // 16 <= 64
+        h2 = self.f32(rows, cout, HW)
+        if (self.u.gca_epilogue_pool and cout % 64 == 0 and cout <= 2048 and HW % 16 == 0 and HW // 16 <= 64
                 and self.pipe_ok(cout, 0, H, g2, norm, 3) and h.lazy is None and f"{name}.__weff__" in self.w
                 and self.pipe_lds_bytes(H, cout, g2[0], g2[1], g2[2], pool=True) <= LDS_MAX):      # else: the k_gca_pool plan below
             # r03: the softmax pooling of the GlobalContext rides in conv2's epilogue (k_conv_fused_pipe<.., POOL>: context logits
@@ -745,9 +530,9 @@ class _Plan:
         if want_slots:
             out.slots = self.misc.alloc(rows // 16 * (cout // 16) * 2 * 4)
         self.op(OP_GCA, 2, p=(pp, pm, self.wptr(f"{name}.gca.net.0.weight"), self.wptr(f"{name}.gca.net.0.bias"),
-                              hid.ptr), i=(B, cout, (cout + 7) // 8 * 8, hidc, chunks, 0 if getattr(self.u, "gate_t", True) else 1))
+                              hid.ptr), i=(B, cout, (cout + 7) // 8 * 8, hidc, chunks, 0 if self.u.gate_t else 1))
         self.op(OP_GCA, 3, p=(h2.ptr, res.ptr, hid.ptr, self.wptr(f"{name}.gca.net.2.weight"), self.wptr(f"{name}.gca.net.2.bias"),
-                              out.ptr, out.slots or 0), i=(rows, cout, HW, hidc, (hidc + 7) // 8 * 8, 0 if getattr(self.u, "gate_t", True) else 1))
+                              out.ptr, out.slots or 0), i=(rows, cout, HW, hidc, (hidc + 7) // 8 * 8, 0 if self.u.gate_t else 1))
 
     def gca_gate(self, name, h2, cout):
         """GlobalContext gate of h2 (imagen_pytorch.py:916-941): softmax-pooled context -> two 1x1 convs -> sigmoid."""
@@ -772,19 +557,20 @@ class _Plan:
         rows = B * HW
         # large batches at the 32x32 / 16x16 levels: GroupNorm as its own pass + the 3x3 convs on k_conv3_halo (csrc/conv_halo.h, 700-950
         # TFLOP/s from 128 tiles on) beat the GroupNorm-fused weight-streaming kernels, which are built for M of a few tiles
-        big = (rows >= (getattr(self.u, f"unfused_min_rows_{H}", 0) or getattr(self.u, "unfused_min_rows", 1 << 30)) and H % 16 == 0 and cin % 64 == 0
-               and cout % 64 == 0)                  # (unfused_min_rows_16 / _32: a per-level threshold, 0 = unfused_min_rows)
+        lvl = getattr(self.u, f"unfused_min_rows_{H}") if H in (4, 8, 16, 32) else 0      # the level's own threshold; 0 = none
+        big = (rows >= (lvl or self.u.unfused_min_rows) and H % 16 == 0 and cin % 64 == 0
+               and cout % 64 == 0)                  # (unfused_min_rows_16 / _32: 0 = unfused_min_rows)
         # r06: the 4x4 / 8x8 levels of large batches likewise (their 3x3 convs then run on k_conv_glds with split-K groups, conv(): lds_mid_min_rows)
-        low = getattr(self.u, f"unfused_min_rows_{H}", 0) if H in (4, 8) else 0
-        big = big or bool(low and rows >= low and getattr(self.u, "lds_mid_min_rows", 0) and cin % 64 == 0 and cout % 64 == 0)
-        if getattr(self.u, "fused", False) and not big:
+        low = lvl if H in (4, 8) else 0             # (unfused_min_rows_4 / _8: 0 = never)
+        big = big or bool(low and rows >= low and self.u.lds_mid_min_rows and cin % 64 == 0 and cout % 64 == 0)
+        if self.u.fused and not big:
             y = self.resnet_fused(name, x, skip, cout, H, gca, cross)
             if y is not None:
                 return y
         a1 = self.bf16(rows, cin, HW)
         raw = self.bf16(rows, cin, HW) if cin != cout else None
         self.gn_act(x, skip, f"{name}.block1.groupnorm", 0, a1, raw)
-        h = self.zf32(rows, cout, HW)
+        h = self.f32(rows, cout, HW)
         self.conv(a1, False, H, H, f"{name}.block1.project.weight", f"{name}.block1.project.bias", h, cout, 0, cout, 3, 1, 1,
                   defer=True)                                  # block2's GroupNorm statistics pass reduces the partials
         if cross:
@@ -792,10 +578,10 @@ class _Plan:
         a2 = self.bf16(rows, cout, HW)
         ss_ptr = self.ss.ptr + self.u.ss_offset[name] * 4
         self.gn_act(h, None, f"{name}.block2.groupnorm", ss_ptr, a2)
-        out = self.zf32(rows, cout, HW)
+        out = self.f32(rows, cout, HW)
         w2, b2 = f"{name}.block2.project.weight", f"{name}.block2.project.bias"
         if gca:
-            h2 = self.zf32(rows, cout, HW)
+            h2 = self.f32(rows, cout, HW)
             self.conv(a2, False, H, H, w2, b2, h2, cout, 0, cout, 3, 1, 1, defer=True)   # reduced by the gca logits pass
             pooled = _T(self.zero.alloc(B * cout * 4), B, cout)        # accumulated with atomics: zeroed per eval
             hid = self.f32(B, max(3, cout // 2))
@@ -824,7 +610,7 @@ class _Plan:
         return out
 
     def _attn_out(self, name, att, x, d, rows):
-        o = self.zf32(rows, d)
+        o = self.f32(rows, d)
         self.conv(att, False, 1, rows // self.B, f"{name}.to_out.0.weight", None, o, d, 0, d, 1)
         y = self.f32(rows, d, x.HW)
         self.ln(o, f"{name}.to_out.1.g", None, y, d, rows, out_f32=True, resid=x)
@@ -835,7 +621,7 @@ class _Plan:
         """Geometry of a fused linear on a 4x4 token map, or None (the first-round ops then run)."""
         if x.HW != 16 or x.rows != self.B * 16:
             return None
-        if x.rows >= getattr(self.u, "unfused_lin_min_rows", 1 << 30) and getattr(self.u, "lds_mid_min_rows", 0):
+        if x.rows >= self.u.unfused_lin_min_rows and self.u.lds_mid_min_rows:
             return None     # r06: enough token rows for 128-row MFMA tiles -- LayerNorm pass + LDS-tiled 1x1 convs (conv(): lds_mid_min_rows)
         return self.fused_geometry(4, x.C, N, norm, 1)
 
@@ -854,7 +640,7 @@ class _Plan:
         if g2 is None:
             return None
         self.need(x)       # split-K slabs: one reduce launch beats re-reducing them in each of the projection's 40 workgroups
-        qkv = self.zf32(rows, nq, 16)
+        qkv = self.f32(rows, nq, 16)
         self.fconv(x, None, 4, f"{name}.to_q.weight" if cross else f"{name}.__qkv__", None, qkv, nq, 1, FNORM_LN, g1,
                    gname=f"{name}.norm.g", silu=False)
         nk = self.wptr(f"{name}.null_kv")
@@ -868,10 +654,10 @@ class _Plan:
                 segs.append((ckvp, ckvp + dh * 4, 2, 2 * dh, self.u.tb_stride, 0))
             kp = qkv.ptr + inner * 4                           # one shared k/v head right of the 8 query heads
             segs += [(nk, nk + dh * 4, 1, 0, 0, 0), (kp, kp + dh * 4, 16, nq, 16 * nq, 0)]
-        o = self.zf32(rows, d, 16)
+        o = self.f32(rows, d, 16)
         # (the guard mirrors fused_host.h: the TOTAL number of keys, <= 4 if any segment keeps its own k / v per head, else <= 24)
         nkeys, per_head = sum(sg[2] for sg in segs), any(sg[5] for sg in segs if sg[2])
-        if getattr(self.u, "attn_in_out_proj", True) and heads == 8 and dh == 64 and len(segs) <= 3 and 1 <= nkeys <= (4 if per_head else 24):
+        if self.u.attn_in_out_proj and heads == 8 and dh == 64 and len(segs) <= 3 and 1 <= nkeys <= (4 if per_head else 24):
             # r04: the attention core runs in the prologue of its output projection (k_conv_fused<.., FNORM_ATTN>: wave = head, the 64
             # workgroups each redo the 16-token core -- 0.3 MFLOP -- instead of one more dependent launch)
             qv = _T(qkv.ptr, rows, inner, 16)
@@ -885,7 +671,7 @@ class _Plan:
 
     def cross_attention(self, name, h):
         """h + CrossAttention(h, context=c)  (imagen_pytorch.py:731-805; keys = [null, 2 time tokens])."""
-        if getattr(self.u, "fused", False):
+        if self.u.fused:
             y = self.attention_fused(name, h, False, True)
             if y is not None:
                 return y
@@ -894,7 +680,7 @@ class _Plan:
         inner = heads * dh
         xn = self.bf16(rows, d)
         self.ln(h, f"{name}.norm.g", None, xn, d, rows)
-        q = self.zf32(rows, inner)
+        q = self.f32(rows, inner)
         self.conv(xn, False, 1, rows // B, f"{name}.to_q.weight", None, q, inner, 0, inner, 1)
         att = self.bf16(rows, inner)
         nk = self.wptr(f"{name}.null_kv")
@@ -905,7 +691,7 @@ class _Plan:
 
     def self_attention(self, name, x, context):
         """x + Attention(x[, context=c])  (imagen_pytorch.py:480-566; one shared k/v head)."""
-        if getattr(self.u, "fused", False):
+        if self.u.fused:
             y = self.attention_fused(name, x, context, False)
             if y is not None:
                 return y
@@ -914,7 +700,7 @@ class _Plan:
         inner = heads * dh
         xn = self.bf16(rows, d)
         self.ln(x, f"{name}.norm.g", None, xn, d, rows)
-        q, kv = self.zf32(rows, inner), self.zf32(rows, 2 * dh)
+        q, kv = self.f32(rows, inner), self.f32(rows, 2 * dh)
         self.conv(xn, False, 1, rows // B, f"{name}.to_q.weight", None, q, inner, 0, inner, 1)
         self.conv(xn, False, 1, rows // B, f"{name}.to_kv.weight", None, kv, 2 * dh, 0, 2 * dh, 1)
         segs = []
@@ -932,26 +718,26 @@ class _Plan:
         B, d, rows = self.B, x.C, x.rows
         x1 = self.self_attention(f"{name}.layers.0.0.fn", x, True)
         hid = int(d * self.u.ff_mult)
-        if getattr(self.u, "fused", False):                      # ChanFeedForward with both ChanLayerNorms inside the 1x1 convs
+        if self.u.fused:                      # ChanFeedForward with both ChanLayerNorms inside the 1x1 convs
             ga, gb = self.lin_geometry(x1, hid, FNORM_LN), None
             if ga is not None and hid % 32 == 0:
-                f1 = self.zf32(rows, hid, 16)
+                f1 = self.f32(rows, hid, 16)
                 gb = self.lin_geometry(f1, d, FNORM_LN)
             if ga is not None and gb is not None:
                 # GELU once, in ff1's epilogue (the 64 workgroups of ff2 would each redo it on the whole 16 x 2048 input)
                 self.fconv(x1, None, 4, f"{name}.layers.0.1.1.weight", None, f1, hid, 1, FNORM_LN, ga,
                            gname=f"{name}.layers.0.1.0.g", silu=False, out_gelu=True)
-                x2 = self.zf32(rows, d, x.HW)
+                x2 = self.f32(rows, d, x.HW)
                 self.fconv(f1, None, 4, f"{name}.layers.0.1.4.weight", None, x2, d, 1, FNORM_LN, gb,
                            gname=f"{name}.layers.0.1.3.g", silu=False, resid=x1)
                 return x2
         xn = self.bf16(rows, d)
         self.ln(x1, f"{name}.layers.0.1.0.g", None, xn, d, rows)
-        f1 = self.zf32(rows, hid)
+        f1 = self.f32(rows, hid)
         self.conv(xn, False, 1, rows // B, f"{name}.layers.0.1.1.weight", None, f1, hid, 0, hid, 1)
         xn3 = self.bf16(rows, hid)
         self.ln(f1, f"{name}.layers.0.1.3.g", None, xn3, hid, rows, gelu=True)
-        x2 = self.zf32(rows, d, x.HW)
+        x2 = self.f32(rows, d, x.HW)
         self.conv(xn3, False, 1, rows // B, f"{name}.layers.0.1.4.weight", None, x2, d, 0, d, 1, resid=x1)
         return x2
 
@@ -1001,7 +787,7 @@ class _Plan:
         xin = self.f32(B * HW, cpad, HW)
         self.op(OP_ELTWISE, 2, p=(self.cond_in.ptr, self.x_in.ptr, 0, xin.ptr), i=(B, HW, u.cond_images_channels, u.channels, cpad))
         # init conv: CrossEmbedLayer k = 3 / 7 / 15 into channel slices (:1017-1042)
-        x = self.zf32(B * HW, u.dim, HW)
+        x = self.f32(B * HW, u.dim, HW)
         co = 0
         for i, k in enumerate((3, 7, 15)):
             cw = u.spec_shapes[f"init_conv.convs.{i}.weight"][0]
@@ -1014,7 +800,7 @@ class _Plan:
         self.x0, self.base = x, self.f32(B * HW, u.dim, HW)
         full_ops, full_written, self.ops, self.written = self.ops, self.written, [], set()
         cws = [u.spec_shapes[f"init_conv.convs.{i}.weight"][0] for i in range(3)]
-        if (getattr(u, "initx_direct", True) and u.fused and R % 8 == 0 and u.channels <= 4 and cws[0] in (64, 128)
+        if (u.initx_direct and u.fused and R % 8 == 0 and u.channels <= 4 and cws[0] in (64, 128)
                 and cws[1] in (32, 64) and cws[2] in (32, 64) and "__init_xw__" in self.w):
             # ONE launch (csrc/initx.hip: MFMA straight out of a [row][column][4 channels] LDS patch) instead of pack + 3 implicit
             # GEMMs + reduce
@@ -1042,18 +828,18 @@ class _Plan:
                 x = self.transformer(f"downs.{lv}.3", x)
             hiddens.append(x)
             if lv < n_lv - 1:
-                y = self.zf32(B * (H // 2) ** 2, do, (H // 2) ** 2)
+                y = self.f32(B * (H // 2) ** 2, do, (H // 2) ** 2)
                 # split-K partials stay in the workspace: the consumer (slot pass / 4x4 GroupNorm prologue) reduces them
                 # (into the 4x4 level: k_conv4_gn gathers at most 4 slabs -- more would send its consumer to the general kernel, silently: ADVICE r05)
                 self.conv(x, True, H, H, f"downs.{lv}.4.weight", f"downs.{lv}.4.bias", y, do, 0, do, 4, 2, 1, defer=bool(u.fused),
-                          defer_max_groups=4 if (H // 2 == 4 and getattr(u, "conv4", True)) else 8)
+                          defer_max_groups=4 if (H // 2 == 4 and u.conv4) else 8)
                 H //= 2
             else:
-                y = self.zf32(B * H * H, do, H * H)
+                y = self.f32(B * H * H, do, H * H)
                 # Parallel(conv3x3, conv1x1) of the last level (imagen_pytorch.py:1294-1297: the two outputs are summed) = ONE 3x3
                 # conv whose centre tap carries the 1x1 weights too (merged at pack time, Unet._packed): one launch and one
                 # 18.9 MB weight stream instead of two launches + a split-K reduction; its partials stay lazy for mid_block1
-                if (B == 1 and u.fused and getattr(u, "conv4", True) and getattr(u, "merged_down_conv4", True) and H == 4 and x.C == do == 1024
+                if (B == 1 and u.fused and u.conv4 and u.merged_down_conv4 and H == 4 and x.C == do == 1024
                         and x.rows == 16 and (x.lazy is None or x.lazy[0] != "splitk")):
                     # r06: ... on k_conv4_gn's un-normalised form (csrc/fused_conv4.h, NORM = false): 4 slices of 256 channels, slabs out
                     # (13.5 -> ~7 us at B = 1; k_conv_igemm keeps it for B >= 2, where k_conv4_gn_mb has no such form)
@@ -1062,7 +848,7 @@ class _Plan:
                                silu=False)
                 else:
                     self.conv(x, True, H, H, f"downs.{lv}.4.__merged__.weight", f"downs.{lv}.4.__merged__.bias", y, do, 0, do, 3, 1, 1,
-                              defer=bool(u.fused), defer_max_groups=4 if (H == 4 and getattr(u, "conv4", True)) else 8)
+                              defer=bool(u.fused), defer_max_groups=4 if (H == 4 and u.conv4) else 8)
             x = y
         mid = x.C
         x = self.resnet("mid_block1", x, None, mid, H, cross=True)
@@ -1078,7 +864,7 @@ class _Plan:
             if ui < n_lv - 1:
                 y = self.f32(B * 4 * H * H, di, 4 * H * H)
                 self.conv(x, True, H, H, f"ups.{ui}.3.net.0.weight", f"ups.{ui}.3.net.0.bias", y, di, 0, di * 4, 1, pixshuf=True,
-                          want_slots=bool(u.fused and getattr(u, "producer_slots", True)))
+                          want_slots=bool(u.fused and u.producer_slots))
                 H *= 2
                 x = y
         x = self.resnet("final_res_block", x, None, u.dim, H, gca=True)
@@ -1087,18 +873,18 @@ class _Plan:
         # emitted, looked at the result and popped the op again, which left the first attempt's workspace reservation, `written`
         # entry and a possible reduce op of the workspace's previous owner in the plan)
         _, _, fgroups = u.conv_tiling((B * HW + 15) // 16, (u.channels + 15) // 16, 9 * (x.C // 32), False)
-        if getattr(u, "producer_slots", True) and fgroups > 1 and (u.channels + 15) // 16 < 4:      # (n_frags < 4: never the LDS-tiled kernel)
+        if u.producer_slots and fgroups > 1 and (u.channels + 15) // 16 < 4:      # (n_frags < 4: never the LDS-tiled kernel)
             o = _T(self.out.ptr, B * HW, u.channels, HW)
             self.conv(x, True, R, R, "final_conv.weight", "final_conv.bias", o, u.channels, 0, u.channels, 3, 1, 1, nchw=True)
             assert self.last_conv_nchw, "final conv: the split-K reduction was expected to write NCHW"
         else:                                                        # rows, then unpack
-            o = self.zf32(B * HW, u.channels, HW)
+            o = self.f32(B * HW, u.channels, HW)
             self.conv(x, True, R, R, "final_conv.weight", "final_conv.bias", o, u.channels, 0, u.channels, 3, 1, 1)
             self.op(OP_ELTWISE, 3, p=(o.ptr, 0, 0, self.out.ptr), i=(B, HW, u.channels, u.channels))
         # r04: the sampler's init conv (k_init_x) leaves the statistics slots of x0 itself.  The full plan's k_slots pass over x0 --
         # emitted by the first GroupNorm-fused conv, i.e. the first op behind the init convs -- then belongs to the init part only.
         first = self.ops[self.n_init_ops] if self.n_init_ops < len(self.ops) else None
-        if (getattr(u, "producer_slots", True) and first is not None and first.type == OP_SLOTS and first.p[0] == self.x0.ptr and not first.p[1]
+        if (u.producer_slots and first is not None and first.type == OP_SLOTS and first.p[0] == self.x0.ptr and not first.p[1]
                 and not first.p[5] and self.x0.slots and len(self.init_x_ops) == 1 and self.init_x_ops[0].type == OP_INITX):
             self.init_x_ops[0].p[4] = self.x0.slots
             self.n_init_ops += 1
@@ -1120,10 +906,6 @@ class _Plan:
             self.x0_view, self.base_view = self.tview(self.x0), self.tview(self.base)
         return self
 
-    def tview(self, t):
-        """torch view of a planned fp32 buffer of the misc arena (static input / output staging)."""
-        off = t.ptr - self.misc.buf.data_ptr()
-        return self.misc.buf[off:off + t.rows * t.C * 4].view(torch.float32).view(t.rows, t.C)
 
 
 class _TimePlan(_Plan):
@@ -1140,7 +922,7 @@ class _TimePlan(_Plan):
         return self
 
 
-class Unet(nn.Module):
+class Unet(PlanOwner, nn.Module):
     def __init__(self, *, dim, dim_mults=(1, 2, 4, 8), num_resnet_blocks=1, layer_attns=True, layer_cross_attns=True,
                  cond_images_channels=0, channels=3, channels_out=None, attn_pool_text=True, cond_dim=None,
                  attn_dim_head=64, attn_heads=8, ff_mult=2., learned_sinu_pos_emb_dim=16, max_conditional_len=256,
@@ -1199,41 +981,8 @@ class Unet(nn.Module):
                 self.tb_off[name[:-len(".to_kv.weight")]] = off
                 off += 2 * shape[0]
         self.tb_stride = (off + 63) // 64 * 64
-        self.conv_waves_target = 1024       # waves wanted per conv launch (4 per CU) before split-K stops
-        self.lds_conv_min_blocks = 96       # use k_conv_lds when a layer has at least this many 128 x 128 output tiles
-        self.lds_mid_min_rows = 128      # r06: convs of >= this many rows that have too few 128-row tiles for lds_conv_min_blocks run on the LDS-tiled kernels with split-K groups (_Plan.conv); 0 = off
-        self.merged_down_conv4 = True     # r06: the merged 3x3 + 1x1 conv of the last Downsample on k_conv4_gn<64, 0, false> at B = 1; False: k_conv_igemm
-        self.rc_small_tiles = 32         # r06: bit mask of map sides (32 | 16 | 8) whose B >= 2 (conv1 || res_conv) pairs keep the B = 1 tile of k_conv3s_rc (32: B = 2 eval 1.155 -> 1.139 ms, B = 4 1.562 -> 1.520; 32 | 16: B = 4 1.580, B = 8 2.451 -> 2.550)
-        self.gn_one = True               # r06: GroupNorm passes of B >= 32 plans (B * 8 >= 256 workgroups) in one launch (k_gn_one); False: k_gn_stats + k_gn_apply everywhere
-        self.lds_mid_min_batch = 8       # ... in plans of at least this many images (the B = 1 .. 4 plans keep their measured kernels)
-        self.unfused_min_rows_4 = 256    # r06: 4x4-level ResnetBlocks with B*16 >= this leave the fused kernels (as unfused_min_rows at 32x32 / 16x16; measured: B = 8 loses 0.12 ms, B = 16 gains 0.22, B = 32 0.49); 0 = never
-        self.unfused_min_rows_8 = 1024   # ... 8x8 level (k_conv3_halo_sm; measured: B = 8 loses 0.14 ms, B = 16 gains 0.04, B = 32 0.56)
-        self.unfused_lin_min_rows = 256      # r06: attention / feed-forward linears of the 4x4 level with >= this many token rows leave the fused kernels (measured: B = 16 3.683 -> 3.670 ms, B = 32 4.664 -> 4.472)
-        self.unfused_min_rows_16 = 4096  # r06: the 16x16 level's own threshold (0 = unfused_min_rows; measured with k_gemm_rows_ks / the r06 plans: B = 16 3.641 -> 3.313 ms; 2048 rows lose: B = 8 2.454 -> 2.512)
-        self.unfused_min_rows_32 = 0     # ... 32x32 level (4096 rows lose: B = 4 1.575 -> 1.686 ms)
-        self.unfused_min_rows = 8192     # ResnetBlocks with B*H*W >= this at the 32x32 / 16x16 levels leave the fused kernels (_Plan.resnet; measured r03: B = 8 eval 3.33 -> 2.96 ms, B = 32 11.5 -> 7.8 ms, B = 4 unchanged)
-        self.lazy_consumers = 3             # bit 0: split-K reductions, bit 1: gated residuals are materialised by their first consumer
-        # Planner attributes (plain Python attributes since r04 -- the SF_* environment switches of the r01-r03 A/B runs are retired;
-        # tools/unet_time.py sets them through SF_UNET_ATTRS, tests/test_gpu_unet.py::test_plan_switches_match_oracle covers them).
-        # GroupNorm inside the conv launches (k_conv_fused) wherever the layer fits; False = the first-round plan
-        self.fused = True
-        self.pair_res_conv = True           # conv1 || res_conv of a ResnetBlock in one launch
-        self.res_conv_beside_pool = True    # 4x4 gca blocks: the res_conv shares the GlobalContext pooling launch instead
-        self.initx_direct = True            # latent half of the init conv as one direct-convolution launch
-        self.big_tile_min_batch = 2         # batch from which the 8x8 / 16x16 / 32x32 maps use 32- / 32- / 64-pixel tiles (r03: B = 2 eval 1.70 -> 1.50 ms, B = 4 2.62 -> 2.02, B = 32 16.4 -> 11.5; at B = 1 they would leave half the CUs idle; 999 = never)
-        self.gca_epilogue_pool = True       # GlobalContext pooling in conv2's epilogue (False = k_gca_pool launch)
-        self.fconv_pipe = True              # slot-GroupNorm 3x3 convs on k_conv_fused_pipe (staging || matrix work)
-        self.producer_slots = True          # r04: k_init_x / the Upsample epilogue leave their consumers' statistics slots, the final conv's split-K reduction writes NCHW (False: the r03 k_slots / k_unpack_out launches; parity tests)
-        self.attn_in_out_proj = True        # the 16-token attention core in the prologue of its output projection (False: k_attn16 launch; parity tests)
-        self.ln_wave = True                 # r05: LayerNorm of <= 256 rows of 512 | 1024 | 2048 channels on k_layernorm_wave (False: op flag 4 = k_layernorm)
-        self.gate_t = True                  # r05: GlobalContext gate with a compile-time hidden width (k_gca_gate_t; False: k_gca_gate)
-        self.conv4_reduce_min_batch = 4     # r05: from this batch on a 4x4 split-K conv1 is reduced by its own launch instead of by conv2's gather (0 = never)
-        self.conv4_mb = True                # r05: even B: the 4x4 GroupNorm-self convs run 2 | 4 images per workgroup (k_conv4_gn_mb; False = op field i[19] bit 0)
-        self.conv4_slices_max_batch = 4     # r05: up to this batch the 4x4 GroupNorm-self convs keep 4 input-channel slices (= k_conv4_gn's geometry); 0 = the workgroup-count rule alone
-        self.conv3s = True                  # r06: the recurring single-source slot-GroupNorm 3x3 convs on k_conv3s (compile-time geometry, csrc/fused_conv3s.h); False: op field i[19] bit 1 = k_conv_fused_pipe
-        self.conv3s_tw32, self.conv3s_tw16, self.conv3s_tw8 = 8, 4, 0      # r06: tile width of k_conv3s's 2-D pixel tiles per map size (0 = full-width strips)
-        self.conv4 = True                   # r05: the 4x4 level's GroupNorm-self 3x3 convs on k_conv4_gn (csrc/fused_conv4.h); False: op flag 128 = k_conv_fused (parity tests)
-        self.use_hip_graph = True           # replay one captured hipGraph per eval instead of ~370 host launches
+        for name, default, _ in SWITCHES:
+            setattr(self, name, default)
         self._pack_cache = None
         self._plans = {}
         self.tile_override = dict(TILE_PICKS)
@@ -1252,38 +1001,17 @@ class Unet(nn.Module):
         fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
         return (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(fan_in)
 
-    def conv_tiling(self, m_frags, n_frags, KS, pixshuf=False):
-        """(WM, WN, split-K groups) of one implicit-GEMM launch, by a small cost model.  A wave owns a
-        (16*WM x 16*WN) tile; the 4 waves of a workgroup split K four ways (reduced in LDS); `groups` further K
-        slices go through the workspace + k_splitk_reduce.  Terms: weight streaming from HBM (needs ~4 waves/CU
-        to saturate), fragment traffic from L2 (1 KiB per fragment, amortised over the tile), MFMA issue, and the
-        partial-tile round trip of split-K."""
-        ov = getattr(self, "tile_override", None)               # {(m_frags, n_frags, KS, pixshuf): (WM, WN, groups)}: measured picks
-        if ov and (m_frags, n_frags, KS, bool(pixshuf)) in ov:  # (TILE_PICKS below) and tools/tile_sweep.py
-            return ov[(m_frags, n_frags, KS, bool(pixshuf))]
-        best = None
-        mfma = m_frags * n_frags * KS
-        w_bytes = n_frags * KS * 1024
-        for WM in (1, 2, 4):
-            if m_frags % WM or (m_frags <= 4 and WM != m_frags and m_frags in (1, 2, 4)):
-                continue                                   # small maps: all rows in one tile -> weights fetched once
-            for WN in (1, 2, 4):
-                if n_frags % WN:
-                    continue
-                tiles = (m_frags // WM) * (n_frags // WN)
-                for groups in ((1,) if pixshuf else (1, 2, 4, 8, 16, 32)):
-                    if groups > 1 and KS // (4 * groups) < 2:
-                        continue
-                    waves = tiles * groups * 4
-                    util = min(1.0, waves / self.conv_waves_target)
-                    t_hbm = w_bytes / 4.0e12 / util
-                    t_l2 = mfma * 1024 * (1.0 / WN + 1.0 / WM) / 12.0e12 / util
-                    t_mfma = mfma * 20 / (1024 * 2.1e9) / util
-                    t_part = (2.0 * groups * m_frags * n_frags * 1024 / 3.0e12 + 2.0e-6) if groups > 1 else 0.0
-                    cost = max(t_hbm, t_l2, t_mfma) + t_part + 1e-9 * WM * WN
-                    if best is None or cost < best[0]:
-                        best = (cost, WM, WN, groups)
-        return best[1], best[2], best[3]
+    def set_switches(self, spec):
+        """Set planner switches from "name=int,name=int" (A/B runs: SF_UNET_ATTRS of tools/unet_time.py, tools/graph_ablate.py) and
+        retire the plans built so far.  A name that is not in SWITCHES is a KeyError: it would create a fresh attribute nobody reads."""
+        pairs = [kv.split("=") for kv in spec.split(",") if kv]
+        unknown = [name for name, _ in pairs if name not in {n for n, _, _ in SWITCHES}]
+        if unknown:
+            raise KeyError(f"Unet.set_switches: no planner switch named {unknown} (unet.SWITCHES)")
+        for name, value in pairs:
+            setattr(self, name, int(value))
+        self.drop_plans()
+        return self
 
     # ---- reference API odds and ends
     def cast_model_parameters(self, *, lowres_cond, conditional_embed_dim, channels, channels_out, cond_on_z):

@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .unet import (OP_ELTWISE, OP_MEMSET, Unet, _Plan, _register, _T)
+from .plan import OP_ELTWISE, OP_MEMSET, Plan, PlanOwner, _T
+from .unet import _register
 
 SD_VAE_DDCONFIG = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=(1, 2, 4, 4),
                        num_res_blocks=2, attn_resolutions=(), dropout=0.0)          # sd-vae.yaml:6-20
@@ -84,7 +85,7 @@ def vae_param_spec(*, ch, ch_mult, num_res_blocks, in_channels, out_ch, z_channe
     return out
 
 
-class _VaePlan(_Plan):
+class _VaePlan(Plan):
     """Static launch plan of one direction ('enc' or 'dec') at batch B."""
 
     def __init__(self, vae, kind, B, device, sizing=None):
@@ -103,11 +104,11 @@ class _VaePlan(_Plan):
         rows, HW, cin = x.rows, H * H, x.C
         a1 = self.bf16(rows, cin, HW)
         self.gn(x, p + ".norm1", a1)
-        h = self.zf32(rows, cout, HW)
+        h = self.f32(rows, cout, HW)
         self.conv3(a1, False, H, p + ".conv1", h, cout)
         a2 = self.bf16(rows, cout, HW)
         self.gn(h, p + ".norm2", a2)
-        out = self.zf32(rows, cout, HW)
+        out = self.f32(rows, cout, HW)
         tw = self.bf16(rows, cout, HW) if twin else None
         if cin != cout:                                   # out = nin_shortcut(x), then conv2 accumulates into it
             xs = x.twin if self.u.conv_twin else None    # (the producing conv left an operand-type copy: half the bytes, LDS-DMA kernel)
@@ -123,10 +124,10 @@ class _VaePlan(_Plan):
         rows = x.rows
         hn = self.bf16(rows, C, HW)
         self.gn(x, p + ".norm", hn, silu=False)
-        q, k, v = (self.zf32(rows, C, HW) for _ in range(3))
+        q, k, v = (self.f32(rows, C, HW) for _ in range(3))
         for t, n in ((q, "q"), (k, "k"), (v, "v")):
             self.conv(hn, False, H, H, f"{p}.{n}.weight", f"{p}.{n}.bias", t, C, 0, C, 1)
-        att = self.zf32(rows, C, HW)
+        att = self.f32(rows, C, HW)
         lib = _lib.lib()
         kp_elems = lib.sf_conv_packed_elems(HW, C, 1, 1)          # B operand of q.k^T: N = HW keys, K = C
         vp_elems = lib.sf_conv_packed_elems(C, (HW + 31) // 32 * 32, 1, 1)   # B operand of P.v: N = C, K = HW
@@ -145,7 +146,7 @@ class _VaePlan(_Plan):
                 raise NotImplementedError("AttnBlock token count must be a multiple of 32")
             self.op(OP_ELTWISE, 6, p=(s.ptr, 0, 0, pr.ptr), i=(HW, HW), f=(float(int(C) ** (-0.5)),))
             self.conv(pr, False, 1, HW, None, None, ob, C, 0, C, 1, w_ptr=vp, batch=1)
-        out = self.zf32(rows, C, HW)
+        out = self.f32(rows, C, HW)
         self.conv(att, True, H, H, p + ".proj_out.weight", p + ".proj_out.bias", out, C, 0, C, 1, resid=x)
         return out
 
@@ -161,7 +162,7 @@ class _VaePlan(_Plan):
             self.x_in = self.f32(B, v.in_channels * HW)
             xin = self.f32(B * HW, 32, HW)
             self.op(OP_ELTWISE, 2, p=(0, self.x_in.ptr, 0, xin.ptr), i=(B, HW, 0, v.in_channels, 32))
-            h = self.zf32(B * HW, ch, HW)
+            h = self.f32(B * HW, ch, HW)
             self.conv3(xin, True, R, "encoder.conv_in", h, ch)
             H = R
             for lv in range(n_lv):
@@ -169,7 +170,7 @@ class _VaePlan(_Plan):
                     h = self.resnet_block(f"encoder.down.{lv}.block.{b}", h, ch * mult[lv], H,
                                           twin=(b == nres - 1 and lv != n_lv - 1 and v.conv_twin))
                 if lv != n_lv - 1:                        # Downsample: zero pad right/bottom, conv3x3 stride 2 (model.py:72-76)
-                    y = self.zf32(B * (H // 2) ** 2, h.C, (H // 2) ** 2)
+                    y = self.f32(B * (H // 2) ** 2, h.C, (H // 2) ** 2)
                     src = h.twin                          # operand-type copy from the block's conv2 epilogue, when it runs an LDS-tiled kernel
                     ytw = self.bf16(y.rows, h.C, y.HW) if (v.conv_twin and ch * mult[lv + 1] != h.C) else None      # ... and one for the next nin_shortcut
                     self.conv(src if src is not None else h, src is None, H, H, f"encoder.down.{lv}.downsample.conv.weight",
@@ -185,7 +186,7 @@ class _VaePlan(_Plan):
             # finite, so the row lives in the arena that is zeroed at the top of every run
             mo = _T(self.zero.alloc(h.rows * 32 * 4), h.rows, 32, H * H)
             self.conv(a, False, H, H, "encoder.conv_out.weight", "encoder.conv_out.bias", mo, 32, 0, zo, 3, 1, 1)
-            qm = self.zf32(h.rows, 2 * v.embed_dim, H * H)
+            qm = self.f32(h.rows, 2 * v.embed_dim, H * H)
             self.conv(mo, True, H, H, "quant_conv.weight", "quant_conv.bias", qm, 2 * v.embed_dim, 0, 2 * v.embed_dim, 1)
             self.out = self.f32(B, 2 * v.embed_dim * H * H)
             self.op(OP_ELTWISE, 3, p=(qm.ptr, 0, 0, self.out.ptr), i=(B, H * H, 2 * v.embed_dim, 2 * v.embed_dim))
@@ -199,7 +200,7 @@ class _VaePlan(_Plan):
             z = _T(self.zero.alloc(B * HW * 32 * 4), B * HW, 32, HW)     # post_quant_conv output, again a zero-padded 32-wide row
             self.conv(zin, True, H, H, "post_quant_conv.weight", "post_quant_conv.bias", z, 32, 0, v.z_channels, 1)
             block_in = ch * mult[-1]
-            h = self.zf32(B * HW, block_in, HW)
+            h = self.f32(B * HW, block_in, HW)
             self.conv3(z, True, H, "decoder.conv_in", h, block_in)
             h = self.resnet_block("decoder.mid.block_1", h, block_in, H)
             h = self.attn_block("decoder.mid.attn_1", h, H)
@@ -208,7 +209,7 @@ class _VaePlan(_Plan):
                 for b in range(nres + 1):
                     h = self.resnet_block(f"decoder.up.{lv}.block.{b}", h, ch * mult[lv], H, twin=(b == nres and lv != 0 and v.conv_twin))
                 if lv != 0:                               # Upsample: nearest x2 folded into the conv's input addressing (:53-57)
-                    y = self.zf32(B * 4 * H * H, h.C, 4 * H * H)
+                    y = self.f32(B * 4 * H * H, h.C, 4 * H * H)
                     src = h.twin                          # the block's conv2 left an operand-type copy: the 3x3 runs on k_conv3_halo
                     ytw = self.bf16(y.rows, h.C, y.HW) if (v.conv_twin and ch * mult[lv - 1] != h.C) else None      # for the next nin_shortcut
                     self.conv(src if src is not None else h, src is None, 2 * H, 2 * H, f"decoder.up.{lv}.upsample.conv.weight",
@@ -216,7 +217,7 @@ class _VaePlan(_Plan):
                     h, H = y, 2 * H
             a = self.bf16(h.rows, h.C, H * H)
             self.gn(h, "decoder.norm_out", a)
-            o = self.zf32(h.rows, v.out_ch, H * H)
+            o = self.f32(h.rows, v.out_ch, H * H)
             self.conv3(a, False, H, "decoder.conv_out", o, v.out_ch)
             self.out = self.f32(B, v.out_ch * H * H)
             self.op(OP_ELTWISE, 3, p=(o.ptr, 0, 0, self.out.ptr), i=(B, H * H, v.out_ch, v.out_ch))
@@ -256,7 +257,7 @@ class DiagonalGaussianDistribution:
                                + other.logvar, dim=[1, 2, 3])
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(PlanOwner, nn.Module):
     """Drop-in for the inference surface of external/ldm/models/autoencoder.py:285-343."""
 
     def __init__(self, ddconfig=None, lossconfig=None, embed_dim=4, ckpt_path=None, ignore_keys=(), **unsupported):
@@ -278,10 +279,7 @@ class AutoencoderKL(nn.Module):
         for name, shape in vae_param_spec(embed_dim=embed_dim, **dd):
             self.spec_shapes[name] = tuple(shape)
             _register(self, name, nn.Parameter(self._default_init(name, shape, g), requires_grad=False))
-        self.conv_waves_target = 1024
-        self.lazy_consumers = 0                # VAE convs are large-M: no split-K partials worth deferring
-        self.ss_total = 0
-        self.lds_conv_min_blocks = 96
+        self.lds_conv_min_blocks = 96          # (lazy_consumers stays 0: VAE convs are large-M, no split-K partials worth deferring)
         # EXPERIMENTAL, not yet measured: GroupNorm statistics from the producing conv's epilogue (csrc/conv_lds.h) instead of a pass
         # over the tensor; parity-checked on CPU threads (tests/test_hostemu_conv_lds.py)
         self.conv_twin = True             # Upsample convs read an operand-type twin of the block output (r03) instead of the fp32 tensor
@@ -289,8 +287,6 @@ class AutoencoderKL(nn.Module):
         self._pack_cache, self._plans = None, {}
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
-
-    conv_tiling = Unet.conv_tiling
 
     @staticmethod
     def _default_init(name, shape, g):

@@ -1,4 +1,4 @@
-"""CPU interpreter of a UNet launch plan (sparsefusion_amd/unet.py::_Plan built on host memory): checks the PLANNER --
+"""CPU interpreter of a UNet launch plan (sparsefusion_amd/unet.py::_Plan on the emitters of plan.py::Plan, built on host memory): checks the PLANNER --
 operand wiring, lazy tensors, workspaces, slot tables -- without a GPU.  The fused ops (FCONV / SLOTS / GCA) run the
 product's own kernel source on CPU threads (hostemu/fused.py); the first-round ops, whose kernels are validated on the
 GPU by tests/test_gpu_unet_ops.py, are restated here in torch from their operand contracts (csrc/unet_ops.hip).

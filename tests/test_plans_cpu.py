@@ -1,6 +1,6 @@
 """Planner invariants checked WITHOUT a GPU: every model's static launch plan is built in sizing mode (fake device
 pointers) and its op list is audited -- operand presence, alignment contracts of the kernels, op-code agreement with the
-C header, lazy tensors all consumed.  Guards the host logic of unet.py / vae.py / lpips.py / eft.py."""
+C header, lazy tensors all consumed.  Guards the host logic of plan.py / unet.py / vae.py / lpips.py / eft.py."""
 import re
 import os
 
@@ -483,6 +483,31 @@ def test_unet_plans_of_every_batch_regime_pass_the_op_audit():
         plan = _Plan(net, B, CPU, (s.zero.off, s.misc.off + s.ws_bytes + s.ws2_bytes + 512, s.ws_bytes, s.ws2_bytes)).build()
         assert _audit(plan.ops, f"unet B={B}", sized=True) >= 91
         assert plan.ws_owner is None or plan.ws_owner.lazy is None
+
+
+def test_set_switches_rejects_unknown_names_and_changes_the_plan():
+    """Unet.set_switches("a=0,b=1") is how an A/B run names planner switches (SF_UNET_ATTRS of tools/unet_time.py, tools/graph_ablate.py): a
+    name that is not in unet.SWITCHES raises KeyError and sets nothing (a misspelt switch used to create a fresh attribute: the A/B then
+    measured the default plan twice); a correct one changes the op list, and every table entry is the attribute Unet.__init__ sets."""
+    from sparsefusion_amd import unet as U
+    net = U.Unet(channels=4, dim=256, dim_mults=(1, 2, 4, 4), num_resnet_blocks=(2, 2, 2, 2), layer_attns=(False, False, False, True),
+                 layer_cross_attns=(False,) * 4, cond_images_channels=256, attn_pool_text=False)
+    names = [n for n, _, _ in U.SWITCHES]
+    assert len(set(names)) == len(names) and all(getattr(net, n) == d and type(getattr(net, n)) is type(d) for n, d, _ in U.SWITCHES)
+    ops = lambda: [(o.type, o.flags, list(o.i)) for o in U._Plan(net, 1, CPU).build().ops]
+    base = ops()
+    for bad in ("conv4=0,fusde=0", "conv4_batch=0", "Fused=0"):
+        with pytest.raises(KeyError):
+            net.set_switches(bad)
+    assert net.conv4 is True and not hasattr(net, "fusde") and ops() == base        # nothing was set
+    assert net.set_switches("") is net and ops() == base
+    net.set_switches("conv4=0,attn_in_out_proj=0")
+    assert (net.conv4, net.attn_in_out_proj) == (0, 0)
+    changed = ops()
+    assert changed != base and sum(t == U.OP_ATTN for t, _, _ in changed) > sum(t == U.OP_ATTN for t, _, _ in base)
+    assert all(f & 128 for t, f, _ in changed if t == U.OP_FCONV) and not any(f & 128 for t, f, _ in base if t == U.OP_FCONV)
+    net.set_switches("conv4=1,attn_in_out_proj=1")
+    assert ops() == base
 
 
 def test_gn_geometry_restates_run_gn():

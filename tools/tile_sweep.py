@@ -1,4 +1,4 @@
-"""Measured tile picks for the implicit-GEMM launches the cost model of Unet.conv_tiling gets wrong: for every k_conv_igemm
+"""Measured tile picks for the implicit-GEMM launches the cost model of PlanOwner.conv_tiling (plan.py) gets wrong: for every k_conv_igemm
 layer of the canonical B = 1 eval body, try every valid (WM, WN, split-K groups) and time the whole eval (graph replay, as the
 sampler runs it); prints the winners as a dict literal for Unet.TILE_PICKS.    python tools/tile_sweep.py [B]"""
 import os, sys, time, torch
