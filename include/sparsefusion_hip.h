@@ -349,6 +349,8 @@ int sf_fusion_loss_backward(const float* img, const float* pred, const float* vi
                             const float* grad_loss, float* grad_img, float* grad_sil, void* stream);
 
 int sf_plan_run(const sf_op* ops, uint32_t n_ops, void* stream);
+/* Launches of k_conv_igemm_t (compile-time-geometry implicit GEMM, op flag 512) this process has made so far: dispatch tests. */
+uint64_t sf_conv_igemm_t_launches(void);
 /* sf_plan_run with a HIP event before every op on the launch stream; h_ms[n_ops] (host) gets per-op
  * elapsed milliseconds.  Synchronises; measurement aid for bench.py (per-kernel roofline). */
 int sf_plan_profile(const sf_op* ops, uint32_t n_ops, void* stream, float* h_ms);

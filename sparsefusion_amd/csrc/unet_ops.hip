@@ -32,6 +32,7 @@
 #include "conv_halo.h"
 #include "conv_halo_small.h"
 #include "conv_igemm.h"
+#include "conv_igemm_t.h"
 #include "attn_ln.h"
 #include <math.h>
 
@@ -69,6 +70,8 @@ __device__ __forceinline__ float wave_max(float v) {
 //          16 = the input is a nearest x2 upsampling of a stored [B, H/2, W/2, Cin] map (H, W = upsampled dims),
 //          32 = ReLU, 64 = GELU(erf) in the epilogue (after bias / residual / accumulate)
 //          256 = the split-K reduction stores NCHW: out[(b * Cout + n) * Ho*Wo + pixel] (the plan's output tensor; groups > 1, not deferred)
+//          512 = planner hint (tile < 256): the launch's geometry is in SF_IGEMM_T_VARIANTS (conv_igemm_t.h) -> k_conv_igemm_t; an op
+//                the table does not hold runs on k_conv_igemm as if the flag were not set (same grid, same operands, same result)
 //   p[7] = (sum, sum of squares) slots of the pixel-shuffled output for the next GroupNorm-fused conv, or NULL (flag 2 only)
 // No atomics: with groups == 1 every output element is owned by one wave (plain store / read-modify-write);
 // with groups > 1 each K-slice group stores its partial tile to the workspace and k_splitk_reduce sums them
@@ -568,6 +571,25 @@ static void launch_conv(const ConvArgs& a, bool a_fp32, int blocks, hipStream_t 
   else k_conv_igemm<WM, WN, false><<<blocks, 256, 0, st>>>(a);
 }
 
+// k_conv_igemm_t (conv_igemm_t.h): the instantiation of a launch's geometry, if there is one.  Returns false (nothing launched) otherwise.
+static unsigned long long g_igemm_t_launches = 0;
+extern "C" uint64_t sf_conv_igemm_t_launches(void) { return g_igemm_t_launches; }
+static bool launch_conv_t(const ConvArgs& a, int WM, int WN, bool a_fp32, int blocks, hipStream_t st) {
+  if (a.B != 1 || a.H != a.W || a.kh != a.kw || a.accum || a.resid || a.relu || a.co_off) return false;
+  const int epi = a.pixshuf ? SF_IGT_PIXSHUF : SF_IGT_SPLITK;
+  if (a.pixshuf ? (!a.slots_out || !a.bias || a.ldc * 4 != a.Cout || a.groups != 1) : (a.groups < 2 || !a.ws)) return false;
+#define SF_TRY_IGT(hl_, cin_, cout_, k_, s_, p_, ups_, wm_, wn_, g_, f32_, epi_) \
+  if (a.H == (1 << hl_) && a.Cin == cin_ && a.Cout == cout_ && a.kh == k_ && a.stride == s_ && a.pad == p_ && a.ups == ups_ && WM == wm_ && \
+      WN == wn_ && a.groups == g_ && a_fp32 == (bool)f32_ && epi == epi_ && a.Ho == ((1 << hl_) + 2 * p_ - k_) / s_ + 1 && a.Wo == a.Ho) { \
+    k_conv_igemm_t<hl_, cin_, cout_, k_, s_, p_, ups_, wm_, wn_, g_, (bool)f32_, epi_><<<blocks, 256, 0, st>>>(a); \
+    ++g_igemm_t_launches; \
+    return true; \
+  }
+  SF_IGEMM_T_VARIANTS(SF_TRY_IGT)
+#undef SF_TRY_IGT
+  return false;
+}
+
 // k_conv_glds (conv_glds.h): the LDS-tiled conv for operand-type activations, staged by LDS-DMA through a ring of NST buffers.
 // Ring depth 4 by default (3 measures the same: the ring is not latency bound; a tile code selects either explicitly, as the tests do).
 static int conv_glds_depth() { return 4; }
@@ -739,6 +761,10 @@ static int run_conv(const sf_op& op, hipStream_t st) {
       SF_FAIL(SF_ERR_INVALID, "conv: unsupported LDS tile %d", bnf);
     }
     SF_CHECK_LAUNCH("conv_lds");
+    return conv_splitk_tail(op, a, M, st);
+  }
+  if ((op.flags & 512) && launch_conv_t(a, WM, WN, f32, blocks, st)) {      // compile-time geometry; no instantiation: the general kernel below
+    SF_CHECK_LAUNCH("conv_igemm_t");
     return conv_splitk_tail(op, a, M, st);
   }
   switch (tile) {

@@ -57,6 +57,8 @@ class PlanOwner:
     tb_stride = 0                   # floats per row of the time block a GroupNorm reads its (scale, shift) from; 0 = none
     lazy_consumers = 0              # bit 0: split-K reductions, bit 1: gated residuals are materialised by their first consumer
     ss_total = 0                    # width of the batched time-MLP output ((scale, shift) of every block); 0 = no time path
+    igemm_t = 0                     # bit j: the launch whose geometry is row j of igemm_t_variants runs on k_conv_igemm_t (op flag 512); 0 = never
+    igemm_t_variants = ()           # the rows of csrc/conv_igemm_t.h SF_IGEMM_T_VARIANTS, in its order (UNet only)
     tile_override = None            # {(m_frags, n_frags, KS, pixshuf): (WM, WN, groups)}: measured picks that replace the cost model (UNet only)
 
     def conv_tiling(self, m_frags, n_frags, KS, pixshuf=False):
@@ -251,8 +253,15 @@ class Plan:
             slots = self.misc.alloc(4 * M // 16 * (ldc // 16) * 2 * 4)
         # nchw: the (non-deferred) split-K reduction of this conv writes the plan's NCHW output directly (was k_unpack_out)
         nchw = bool(nchw and groups > 1 and not defer and not accum and not resid and tile < 256 and co_off == 0 and ldc == Cout)
+        # k_conv_igemm_t (csrc/conv_igemm_t.h): a one-image launch whose whole geometry is a row of the variant table; the host checks the
+        # same conditions and keeps k_conv_igemm for anything else
+        igt = False
+        if self.u.igemm_t and tile < 256 and B == 1 and H == W and (Ho, Wo) == ((H + 2 * pad - k) // stride + 1,) * 2 and not (accum or res or relu or gelu or co_off):
+            key = (H.bit_length() - 1, x.C, Cout, k, stride, pad, int(bool(upsampled)), WM, WN, groups, int(bool(x_f32)), 1 if pixshuf else 0)
+            if key in self.u.igemm_t_variants and H == 1 << key[0] and (self.u.igemm_t >> self.u.igemm_t_variants.index(key)) & 1:
+                igt = bool(slots and bias and ldc * 4 == Cout) if pixshuf else groups > 1
         self.op(OP_CONV, (1 if x_f32 else 0) | (2 if pixshuf else 0) | (4 if accum else 0) | (8 if defer else 0) |
-                (16 if upsampled else 0) | (32 if relu else 0) | (64 if gelu else 0) | (256 if nchw else 0),
+                (16 if upsampled else 0) | (32 if relu else 0) | (64 if gelu else 0) | (256 if nchw else 0) | (512 if igt else 0),
                 p=(x.ptr, w_ptr if w_ptr is not None else self.wptr(wname), bias, out.ptr, res, ws, 0, slots),
                 i=(B, H, W, x.C, Ho, Wo, Cout, ldc, co_off, k, k, stride, pad, groups, tile))
         if defer:

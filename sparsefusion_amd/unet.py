@@ -32,6 +32,11 @@ CONV3S_VARIANTS = {(5, 256, 5, 2, 2), (5, 256, 3, 2, 2), (4, 256, 4, 1, 1), (4, 
                    (4, 256, 2, 2, 1), (4, 256, 2, 2, 2), (4, 512, 2, 2, 2), (3, 512, 3, 2, 1), (3, 1024, 3, 2, 1), (3, 1024, 3, 2, 2)}
 # (log2 H, C1, C2, Cout, log2 tile width, WM, WN) of k_conv3s_rc (SF_CONV3S_RC_VARIANTS): conv1 on a concat + the block's res_conv in one set of workgroups
 CONV3S_RC_VARIANTS = {(5, 256, 256, 256, 3, 2, 2), (4, 512, 256, 512, 2, 1, 2), (3, 1024, 512, 1024, 3, 1, 1)}
+# (log2 H, Cin, Cout, k, stride, pad, ups, WM, WN, split-K groups, A is fp32, epilogue kind 0 split-K / 1 pixel shuffle + slots) of k_conv_igemm_t, in the
+# order of csrc/conv_igemm_t.h SF_IGEMM_T_VARIANTS (tests/test_plans_igemm_t_cpu.py compares the two): bit j of the switch igemm_t = row j
+IGEMM_T_VARIANTS = ((5, 256, 256, 4, 2, 1, 0, 2, 2, 4, 1, 0), (4, 256, 512, 4, 2, 1, 0, 1, 2, 8, 1, 0), (3, 512, 1024, 4, 2, 1, 0, 1, 1, 4, 1, 0),
+                    (2, 1024, 4096, 1, 1, 0, 0, 1, 1, 1, 1, 1), (3, 1024, 2048, 1, 1, 0, 0, 1, 1, 1, 1, 1), (4, 512, 1024, 1, 1, 0, 0, 1, 2, 1, 1, 1),
+                    (5, 256, 4, 3, 1, 1, 0, 1, 1, 4, 1, 0))
 ATTN_LDS_BYTES = 8 * 16 * 36 * 4 + 2 * 8 * 4 * 68 * 4      # SF_ATTN_LDS_BYTES: scratch of the attention prologue (FNORM_ATTN)
 # Measured (WM, WN, split-K groups) of implicit-GEMM launches where the cost model of PlanOwner.conv_tiling picks a slower tile
 # (tools/tile_sweep.py on MI355X, whole-eval time, r03: B = 1 eval 1.3246 -> 1.3004 ms): key = (m_frags, n_frags, KS, pixshuf).
@@ -53,6 +58,7 @@ SWITCHES = (
     ("conv_waves_target", 1024, "waves wanted per conv launch (4 per CU) before split-K stops"),
     ("lds_conv_min_blocks", 96, "use k_conv_lds when a layer has at least this many 128 x 128 output tiles"),
     ("lds_mid_min_rows", 128, "r06: convs of >= this many rows that have too few 128-row tiles for lds_conv_min_blocks run on the LDS-tiled kernels with split-K groups (Plan.conv); 0 = off"),
+    ("igemm_t", 127, "the one-of-a-kind implicit GEMMs of the B = 1 eval on k_conv_igemm_t (compile-time geometry, csrc/conv_igemm_t.h; op flag 512): bit j = row j of IGEMM_T_VARIANTS; 0: k_conv_igemm"),
     ("merged_down_conv4", True, "r06: the merged 3x3 + 1x1 conv of the last Downsample on k_conv4_gn<64, 0, false> at B = 1; False: k_conv_igemm"),
     ("rc_small_tiles", 32, "r06: bit mask of map sides (32 | 16 | 8) whose B >= 2 (conv1 || res_conv) pairs keep the B = 1 tile of k_conv3s_rc (32: B = 2 eval 1.155 -> 1.139 ms, B = 4 1.562 -> 1.520; 32 | 16: B = 4 1.580, B = 8 2.451 -> 2.550)"),
     ("gn_one", True, "r06: GroupNorm passes of B >= 32 plans (B * 8 >= 256 workgroups) in one launch (k_gn_one); False: k_gn_stats + k_gn_apply everywhere"),
@@ -986,6 +992,7 @@ class Unet(PlanOwner, nn.Module):
         self._pack_cache = None
         self._plans = {}
         self.tile_override = dict(TILE_PICKS)
+        self.igemm_t_variants = IGEMM_T_VARIANTS
 
     @staticmethod
     def _default_init(name, shape, g):

@@ -30,7 +30,8 @@ def cls(k):
     if o.type == OP_GCA:
         return "gca_" + {1: "pool", 2: "net0", 3: "gate"}.get(o.flags, str(o.flags)) + f"_{int(round((o.i[2] if o.flags != 2 else 0) ** 0.5))}"
     if o.type == OP_CONV:
-        return f"igemm_{o.i[1]}x{o.i[2]}_k{o.i[9]}" + ("_pixshuf" if o.flags & 2 else "") + ("_deferred" if o.flags & 8 else "")
+        return (f"igemm_{o.i[1]}x{o.i[2]}_k{o.i[9]}" + ("_pixshuf" if o.flags & 2 else "") + ("_deferred" if o.flags & 8 else "")
+                + ("_t" if o.flags & 512 else ""))                  # _t: planned for k_conv_igemm_t (csrc/conv_igemm_t.h)
     return {OP_SLOTS: "slots", OP_LN: "layernorm", OP_ATTN: "attn16", OP_SPLITK_REDUCE: "splitk_reduce", OP_INITX: "init_x", OP_ELTWISE: "eltwise"}.get(o.type, f"op{o.type}")
 
 
