@@ -184,6 +184,15 @@ int sf_ngp_density(const sf_ngp_field* f, const float* xyz, uint32_t P,
 int sf_ngp_density_lattice(const sf_ngp_field* f, const float* ax, const float* ay, const float* az,
                            uint32_t nx, uint32_t ny, uint32_t nz, float* sigma, void* stream);
 
+/* Point attributes (NeRFNetwork.finite_difference_normal / normal, network_grid.py:91-106, 155-164): per point x of xyz [P,3]
+ * sigma [P] and albedo [P,3] exactly as sf_ngp_density gives them; grad [P,3], grad_a = 0.5f * (sp_a - sn_a) / epsilon with
+ * sp_a, sn_a = sigma at clamp(x +- epsilon e_a, -bound, bound) (add and clamp in f32, each bit-identical to sf_ngp_density on
+ * that point), written as computed; normal [P,3] = grad / sqrtf(fmaxf((gx gx + gy gy) + gz gz, 1e-20f)) with NaN written as 0.
+ * Any output may be NULL (not written), at least one is required.  SF_ERR_INVALID, before any device call: NULL f or xyz, all
+ * outputs NULL, epsilon not finite or <= 0.  P == 0 returns SF_OK without a launch. */
+int sf_ngp_point_attrs(const sf_ngp_field* f, const float* xyz, uint32_t P, float epsilon,
+                       float* sigma, float* albedo, float* grad, float* normal, void* stream);
+
 /* Separable Gaussian of scipy.ndimage.gaussian_filter (mode 'reflect', radius int(truncate*sigma + 0.5) <= 64, taps in
  * double, one pass per axis in the order 0, 1, 2, each output rounded to f32).  in and out must not alias.  stats (or NULL)
  * receives {mean, population std} of out in double, reduced in a fixed order (bit-reproducible).

@@ -4,6 +4,7 @@
 #include "sf_common.h"
 #include "mesh_kernels.h"
 #include "ngp_field_lds.h"
+#include "ngp_point_attrs.h"
 
 // sigma at (ax[i], ay[j], az[k]) -> sigma[(i * ny + j) * nz + k], straight from the lattice index (no point buffer).  The per-point
 // code is k_ngp_field's (ngp_render.hip): weights in LDS, the same encode / MLP / activation, so a lattice value is bit-identical
@@ -44,6 +45,46 @@ extern "C" int sf_ngp_density_lattice(const sf_ngp_field* f, const float* ax, co
   k_ngp_lattice<<<sf_grid_cap(sf_div_up((uint64_t)nx * ny * nz, 256)), 256, 0, st>>>(sf_ngp_field_ptrs(f), lv, ax, ay, az, nx, ny, nz,
                                                                                     sigma);
   SF_CHECK_LAUNCH("ngp_density_lattice");
+  return SF_OK;
+}
+
+// sigma, albedo, finite-difference gradient and normal at P points (ngp_point_attrs.h): seven evaluations of the field per thread,
+// one after the other, each bit-identical to sf_ngp_density on its fp32 point.  Launch shape, LDS weights and the barrier at the
+// top of each round as k_ngp_lattice.  Null outputs are skipped; with neither grad nor normal only the centre is evaluated.
+__global__ __launch_bounds__(256) void k_ngp_point_attrs(FieldPtrs f, NgpLevels lv, const float* __restrict__ xyz, uint32_t P, float eps,
+                                                         float* __restrict__ sigma, float* __restrict__ albedo, float* __restrict__ grad,
+                                                         float* __restrict__ normal) {
+  __shared__ __attribute__((aligned(16))) float W[NGP_WTOTAL];
+  load_weights_lds(W, f);
+  const int n_eval = (grad || normal) ? 7 : 1;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < P; base += (uint64_t)gridDim.x * blockDim.x) {
+    __syncthreads();
+    const uint64_t p = base + threadIdx.x;
+    if (p >= P) continue;
+    const float x[3] = {xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2]};
+    NgpPointAttrs a;
+    ngp_point_attrs(lv, f.table, W, f.bound, x, eps, n_eval, a);
+    if (sigma) sigma[p] = a.sigma;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (albedo) albedo[3 * p + c] = a.albedo[c];
+      if (grad) grad[3 * p + c] = a.grad[c];
+      if (normal) normal[3 * p + c] = a.normal[c];
+    }
+  }
+}
+
+extern "C" int sf_ngp_point_attrs(const sf_ngp_field* f, const float* xyz, uint32_t P, float epsilon, float* sigma, float* albedo,
+                                  float* grad, float* normal, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!f || !xyz) SF_FAIL(SF_ERR_INVALID, "ngp_point_attrs: null field or points");
+  if (!sigma && !albedo && !grad && !normal) SF_FAIL(SF_ERR_INVALID, "ngp_point_attrs: at least one output is required");
+  if (!isfinite(epsilon) || !(epsilon > 0.0f)) SF_FAIL(SF_ERR_INVALID, "ngp_point_attrs: epsilon must be finite and > 0");
+  if (P == 0) return SF_OK;
+  NgpLevels lv;
+  if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
+  k_ngp_point_attrs<<<sf_grid_cap(sf_div_up(P, 256)), 256, 0, st>>>(sf_ngp_field_ptrs(f), lv, xyz, P, epsilon, sigma, albedo, grad, normal);
+  SF_CHECK_LAUNCH("ngp_point_attrs");
   return SF_OK;
 }
 

@@ -1,0 +1,65 @@
+// Point attributes of the Instant-NGP field for ONE point: sigma and albedo at the point, the central finite difference of sigma
+// (NeRFNetwork.finite_difference_normal, external/nerf/network_grid.py:91-106) and its safe_normalize'd direction (normal,
+// :155-164; safe_normalize, external/nerf/utils.py:41).  Plain C++ over ngp_device.h, so tests/hostemu compiles the same source
+// for the CPU; the kernel and the host entry point (sf_ngp_point_attrs) are in mesh.hip.  See DESIGN.md section 9.
+//
+// Seven evaluations of the field, each the per-point code of k_ngp_field (ngp_unit / ngp_encode / ngp_mlp_forward / ngp_blob), so
+// each is bit-identical to sf_ngp_density on the same fp32 point:
+//   e = 0          the point itself, as given (not clamped, as common_forward does not clamp)
+//   e = 1 .. 6     clamp(x + o, -bound, bound) with o = +eps e_a (odd e) or -eps e_a (even e), a = (e - 1) / 2: the add and the
+//                  clamp in fp32 on ALL three coordinates (the reference adds a [1, 3] tensor whose other two entries are 0.0 and
+//                  clamps the sum), NaN kept as torch.clamp keeps it
+//   grad_a   = 0.5f * (sp_a - sn_a) / eps                      (IEEE division; written as computed: NaN / inf stay visible)
+//   normal   = grad / sqrtf(fmaxf((gx gx + gy gy) + gz gz, 1e-20f)), NaN components -> 0   (no contraction)
+// The evaluations run in a loop that is NOT unrolled, one after the other through the same registers: the register count is that
+// of one evaluation (k_ngp_lattice's), and the latency of a level's eight gathers is hidden by the other waves of the SIMD.
+#pragma once
+#include "ngp_device.h"
+
+struct NgpPointAttrs { float sigma; float albedo[3]; float grad[3]; float normal[3]; };
+
+// torch.clamp(v, -b, b): NaN propagates (fminf / fmaxf alone would return the bound)
+SF_HD float ngp_clamp_sym(float v, float b) { return (v != v) ? v : fminf(fmaxf(v, -b), b); }
+
+// n_eval = 7: everything; n_eval = 1: sigma and albedo only (grad and normal are left untouched)
+SF_HD void ngp_point_attrs(const NgpLevels& lv, const float* __restrict__ table, const float* __restrict__ W, float bound,
+                           const float x[3], float eps, int n_eval, NgpPointAttrs& a) {
+  float sp = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+#pragma unroll 1
+  for (int e = 0; e < n_eval; ++e) {
+    // keeps the loop-invariant weight reads (LDS on the GPU) inside the loop: hoisted, they would be pinned in registers and spill
+    asm volatile("" ::: "memory");
+    const int axis = (e - 1) >> 1;                     // -1 for the centre
+    const float o = (e & 1) ? eps : -eps;
+    float xe[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) xe[d] = e == 0 ? x[d] : ngp_clamp_sym(SF_ADD(x[d], d == axis ? o : 0.0f), bound);
+    float x01[3], feat[NGP_FEAT], h1[NGP_HID], h2[NGP_HID], out[NGP_OUT];
+    const bool inside = ngp_unit(xe, bound, x01);
+    ngp_encode(lv, table, x01, inside, feat);
+    ngp_mlp_forward(W, feat, h1, h2, out);
+    const float s = expf(out[0] + ngp_blob(xe));
+    if (e == 0) {
+      a.sigma = s;
+      a.albedo[0] = ngp_sigmoid(out[1]);
+      a.albedo[1] = ngp_sigmoid(out[2]);
+      a.albedo[2] = ngp_sigmoid(out[3]);
+    } else if (e & 1) {
+      sp = s;
+    } else {
+      const float g = SF_DIV(SF_MUL(0.5f, SF_SUB(sp, s)), eps);
+      if (axis == 0) gx = g;
+      else if (axis == 1) gy = g;
+      else gz = g;
+    }
+  }
+  if (n_eval < 7) return;
+  a.grad[0] = gx;
+  a.grad[1] = gy;
+  a.grad[2] = gz;
+  const float len = sqrtf(fmaxf(SF_ADD(SF_ADD(SF_MUL(gx, gx), SF_MUL(gy, gy)), SF_MUL(gz, gz)), 1e-20f));
+  const float nx = SF_DIV(gx, len), ny = SF_DIV(gy, len), nz = SF_DIV(gz, len);
+  a.normal[0] = (nx != nx) ? 0.0f : nx;
+  a.normal[1] = (ny != ny) ? 0.0f : ny;
+  a.normal[2] = (nz != nz) ? 0.0f : nz;
+}

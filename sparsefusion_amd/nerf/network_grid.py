@@ -8,7 +8,10 @@ Same constructor, state-dict keys and optimiser grouping as the reference's NeRF
 Two execution routes, both on the GPU library:
   * `render` / `run` (inherited): the fused render node (renderer.py);
   * `common_forward` / `density` / `forward` on arbitrary points: fused sf_ngp_density when no
-    gradient is needed, otherwise HIP grid-encode op + torch linears (differentiable)."""
+    gradient is needed, otherwise HIP grid-encode op + torch linears (differentiable);
+  * `finite_difference_normal` / `normal` / `forward(shading='lambertian')`: fused sf_ngp_point_attrs
+    (seven field evaluations per point in one launch) when no gradient is needed, otherwise six
+    `common_forward` calls as the reference composes them."""
 import ctypes as C
 
 import torch
@@ -18,6 +21,7 @@ import torch.nn.functional as F
 from .. import _lib
 from ..gridencoder import GridEncoder
 from .renderer import NeRFRenderer, _FieldHandle
+from .utils import safe_normalize
 
 
 class MLP(nn.Module):
@@ -83,10 +87,12 @@ class NeRFNetwork(NeRFRenderer):
         d = (x ** 2).sum(-1)
         return 5 * torch.exp(-d / (2 * 0.2 ** 2))
 
+    def _needs_grad(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
     def common_forward(self, x):
         """x [N,3] in [-bound,bound] -> sigma [N], albedo [N,3]."""
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if not needs_grad:
+        if not self._needs_grad(x):
             _lib.require_cuda(x)
             xs = x.detach().reshape(-1, 3).float().contiguous()
             sigma = torch.empty(xs.shape[0], dtype=torch.float32, device=xs.device)
@@ -100,11 +106,61 @@ class NeRFNetwork(NeRFRenderer):
         h = self.sigma_net(self.encoder(x, bound=self.bound))
         return trunc_exp(h[..., 0] + self.gaussian(x)), torch.sigmoid(h[..., 1:])
 
+    def _point_attrs(self, x, epsilon, **want):
+        """The fused route (no gradient): one sf_ngp_point_attrs launch, outputs shaped like x."""
+        from .. import mesh
+        out = mesh.point_attributes(self, x, epsilon, **want)
+        return {k: v.view(x.shape[:-1]) if k == 'sigma' else v.view(*x.shape[:-1], 3) for k, v in out.items()}
+
+    def finite_difference_normal(self, x, epsilon=1e-2):
+        """network_grid.py:91-106: central differences of sigma over +-epsilon per axis, the offset points clamped to the box ->
+        [..., 3] (not normalised).  Without a gradient it is one launch (the gradient output of sf_ngp_point_attrs); when a
+        gradient is needed (the rule of common_forward) it is composed from six common_forward calls as the reference does."""
+        if not self._needs_grad(x):
+            return self._point_attrs(x, epsilon, sigma=False, albedo=False, normal=False)['grad']
+        comps = []
+        for a in range(3):
+            side = []
+            for e in (epsilon, -epsilon):
+                o = [0.0, 0.0, 0.0]
+                o[a] = e
+                side.append(self.common_forward((x + torch.tensor([o], device=x.device)).clamp(-self.bound, self.bound))[0])
+            comps.append(0.5 * (side[0] - side[1]) / epsilon)
+        return torch.stack(comps, dim=-1)
+
+    def normal(self, x, smooth=False):
+        """network_grid.py:155-164: safe_normalize(finite_difference_normal(x)) with NaN set to 0."""
+        if smooth:
+            raise NotImplementedError(
+                "normal(smooth=True) is not provided: the reference's smooth variant averages the field over torch.rand_like "
+                "neighbourhoods of every offset point (network_grid.py:108-152), which is not a deterministic function of the field")
+        if not self._needs_grad(x):
+            return self._point_attrs(x, 1e-2, sigma=False, albedo=False, grad=False)['normal']
+        normal = safe_normalize(self.finite_difference_normal(x))
+        return torch.where(torch.isnan(normal), torch.zeros_like(normal), normal)
+
     def forward(self, x, d, l=None, ratio=1, shading='albedo'):
-        if shading != 'albedo':
-            raise NotImplementedError("only shading='albedo' is on the distillation path")
-        sigma, color = self.common_forward(x)
-        return sigma, color, None
+        """network_grid.py:167-197.  'albedo': (sigma, albedo, None).  'lambertian': (sigma, albedo * (ratio + (1 - ratio) *
+        clamp(normal . (-l), min=0)), normal), with sigma, albedo and normal from ONE launch when no gradient is needed."""
+        if shading == 'albedo':
+            sigma, color = self.common_forward(x)
+            return sigma, color, None
+        if shading in ('normal', 'textureless'):
+            raise NotImplementedError(
+                f"shading={shading!r} uses the reference's smooth normal, an average over torch.rand_like neighbourhoods that is "
+                "not a deterministic function of the field; 'albedo' and 'lambertian' are provided")
+        if shading != 'lambertian':
+            raise ValueError(f"unknown shading {shading!r}")
+        if l is None:
+            raise ValueError("shading='lambertian' needs the light direction l [3]")
+        if not self._needs_grad(x):
+            out = self._point_attrs(x, 1e-2, grad=False)
+            sigma, albedo, normal = out['sigma'], out['albedo'], out['normal']
+        else:
+            sigma, albedo = self.common_forward(x)
+            normal = self.normal(x)
+        lambertian = ratio + (1 - ratio) * (normal @ -l).clamp(min=0)
+        return sigma, albedo * lambertian.unsqueeze(-1), normal
 
     def density(self, x):
         sigma, albedo = self.common_forward(x)

@@ -194,6 +194,25 @@ class NeRFRenderer(nn.Module):
         cuda_ray=False (the reference reads mean_density / density_bitfield, which exist only with cuda_ray).  `S` is accepted
         for call compatibility: the lattice is evaluated without a point buffer, so there are no slabs to bound.  The marching
         cubes' order and winding are this library's own (PyMCubes is not available to pin against)."""
+        return self._export_mesh(path, resolution, None)[:2]
+
+    @torch.no_grad()
+    def export_mesh_attributes(self, path, resolution=None, S=128, epsilon=None):
+        """export_mesh with per-vertex colour and normal from the field: the same lattice, smoothing, level and marching cubes
+        (vertices and faces bit-identical to export_mesh's), then albedo and outward normal at the returned world-coordinate
+        vertices in one launch (mesh.vertex_attributes).  Writes `path/mcubes_mesh.obj` (`v x y z r g b`, `vn`, `f a//a ..`;
+        vertices in index coordinates as export_mesh writes them) and `path/mcubes_mesh.ply` (binary, world coordinates, float
+        normals, uchar colours).  Returns (vertices, faces, colors [V, 3] float32, normals [V, 3] float32).
+
+        `epsilon=None` is one lattice spacing, 2 * bound / (R - 1) -- a choice of this library: the surface comes from a volume
+        smoothed over 1.5 cells, and the reference's 1e-2 (finite_difference_normal's default) probes hash-grid detail far below
+        what the mesh resolves.  An explicit epsilon is honoured.  This is a method of its own, not an `attributes=` argument of
+        export_mesh, so that export_mesh keeps the reference's signature."""
+        R = 128 if resolution is None else int(resolution)
+        return self._export_mesh(path, resolution, 2.0 * self.bound / (R - 1) if epsilon is None else epsilon)
+
+    def _export_mesh(self, path, resolution, epsilon):
+        """epsilon None: geometry only (export_mesh); else also vertex attributes and the PLY file"""
         from .. import mesh
         R = 128 if resolution is None else int(resolution)
         sigmas = mesh.density_lattice(self, R, self.bound)
@@ -201,8 +220,14 @@ class NeRFRenderer(nn.Module):
         mean, std = (float(x) for x in stats.cpu())
         vertices, faces = mesh.marching_cubes(smooth, mean + std * 0.25)
         os.makedirs(path, exist_ok=True)
-        mesh.export_obj(vertices, faces, os.path.join(path, 'mcubes_mesh.obj'))
-        return vertices / (R - 1.0) * (2 * self.bound) - self.bound, faces
+        world = vertices / (R - 1.0) * (2 * self.bound) - self.bound
+        if epsilon is None:
+            mesh.export_obj(vertices, faces, os.path.join(path, 'mcubes_mesh.obj'))
+            return world, faces
+        colors, normals = mesh.vertex_attributes(self, world, epsilon)
+        mesh.export_obj(vertices, faces, os.path.join(path, 'mcubes_mesh.obj'), colors=colors, normals=normals)
+        mesh.export_ply(world, faces, os.path.join(path, 'mcubes_mesh.ply'), colors=colors, normals=normals)
+        return world, faces, colors, normals
 
     @torch.no_grad()
     def update_extra_state(self, decay=0.95, S=128, noise=None):

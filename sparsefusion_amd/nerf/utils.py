@@ -1,8 +1,14 @@
-"""Trainer-side geometry helpers of external/nerf/utils.py:174-204 with the marching cubes on the GPU (sparsefusion_amd.mesh)."""
+"""Trainer-side geometry helpers of external/nerf/utils.py:174-204 with the marching cubes on the GPU (sparsefusion_amd.mesh),
+and safe_normalize (:41)."""
 import numpy as np
 import torch
 
 from .. import mesh
+
+
+def safe_normalize(x, eps=1e-20):
+    """external/nerf/utils.py:41: x / sqrt(clamp(sum(x^2, -1), min=eps))."""
+    return x / torch.sqrt(torch.clamp(torch.sum(x * x, -1, keepdim=True), min=eps))
 
 
 def _device_of(*xs):

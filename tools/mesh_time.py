@@ -2,7 +2,10 @@
 next to the CPU pipeline it is tested against (scipy gaussian_filter + numpy level + tests/mesh_ref.py marching cubes) on the
 same field.  One JSON line per resolution.
 
-    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu]
+    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu] [--attrs]
+
+--attrs adds, per resolution and for a fixed set of 2^20 random points, the one-launch vertex attributes (sf_ngp_point_attrs) next to
+the same quantities composed from seven sf_ngp_density calls and torch glue (what the field API offered before that entry point).
 """
 import argparse
 import json
@@ -67,11 +70,46 @@ def mc_split(sm, iso):
     return e[0].elapsed_time(e[1]), e2.elapsed_time(e[2])
 
 
+def _median_ms(fn, reps):
+    times = []
+    for i in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if i:
+            times.append(e0.elapsed_time(e1))
+    return statistics.median(times)
+
+
+def attrs_time(net, x, eps, reps):
+    """ms of one sf_ngp_point_attrs launch (albedo + normal) and of the composition from seven sf_ngp_density calls on x [P, 3]"""
+    from sparsefusion_amd.nerf.utils import safe_normalize
+
+    def composed():
+        albedo = net.density(x)["albedo"]
+        comps = []
+        for a in range(3):
+            o = torch.zeros(1, 3, device=x.device)
+            o[0, a] = eps
+            sp = net.density((x + o).clamp(-BOUND, BOUND))["sigma"]
+            sn = net.density((x - o).clamp(-BOUND, BOUND))["sigma"]
+            comps.append(0.5 * (sp - sn) / eps)
+        n = safe_normalize(torch.stack(comps, -1))
+        n[torch.isnan(n)] = 0
+        return albedo, n
+
+    return dict(P=int(x.shape[0]), eps=float(eps), one_launch_ms=_median_ms(lambda: mesh.vertex_attributes(net, x, eps), reps),
+                seven_density_calls_ms=_median_ms(composed, reps))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, nargs="+", default=[128, 256])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--attrs", action="store_true")
     a = ap.parse_args()
     golden = torch.load(os.path.join(ROOT, "tests", "golden", "ngp_render.pt"))
     p = params_from_cfg(golden["teacher"]["cfg"])
@@ -98,6 +136,14 @@ def main():
                                     classify_scan=statistics.median(s[0] for s in splits), emit=statistics.median(s[1] for s in splits),
                                     mc_with_readback=med["mc"]), obj_write_ms=med["obj"], export_mesh_wall_ms=total,
                    V=runs[0]["V"], F=runs[0]["F"])
+        if a.attrs:
+            with torch.no_grad():
+                verts, _ = net.export_mesh(tmp, resolution=R)
+                eps = 2.0 * BOUND / (R - 1)
+                g = torch.Generator().manual_seed(3)
+                rand = ((torch.rand(1 << 20, 3, generator=g) * 2 - 1) * BOUND).to(verts.device)
+                out["attrs_vertices"] = attrs_time(net, verts.contiguous(), eps, a.reps)
+                out["attrs_random"] = attrs_time(net, rand, eps, a.reps)
         if not a.no_cpu:
             v = vol.cpu().numpy()
             t0 = time.perf_counter()
