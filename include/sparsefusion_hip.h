@@ -263,6 +263,24 @@ uint64_t sf_ngp_render_forward_workspace_bytes(uint32_t N, uint32_t T);
  * buffer untouched between the two calls. */
 uint64_t sf_ngp_render_cache_bytes(uint32_t N, uint32_t T);
 
+/* Lambertian-shaded render WITHOUT gradient of the same rays (NeRFRenderer.run, shading='lambertian'): first the stages of
+ * sf_ngp_render_forward with no field cache (same arguments, same nears / fars / z_sorted / sigma_s / rgb_s = albedo / depth /
+ * weights_sum, bit for bit), then per sorted sample the point min(max(o + d z, lo), hi), its finite-difference normal (the six
+ * offset evaluations of sf_ngp_point_attrs with `epsilon`; the centre is not re-evaluated) and the colour
+ * albedo * (ambient_ratio + (1 - ambient_ratio) * max(n . -light_d, 0)), then the composite of that colour.
+ * light_d: 3 floats ON THE DEVICE.  Outputs next to the forward's: normal_s, rgb_shaded_s [N,2T,3]; xyz_s [N,2T,3] or NULL;
+ * image [N,3] (shaded, with background); normal_image [N,3] = sum w n (no background) or NULL; orient [N] = sum w max(n . d, 0)^2
+ * or NULL.  SF_ERR_INVALID before any launch: NULL light_d / required output, epsilon not finite or <= 0, ambient_ratio not
+ * finite, T outside [4, 64], N * 2T >= 2^32, workspace below sf_ngp_render_shaded_workspace_bytes(N, T).  N == 0: SF_OK, no launch. */
+int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
+                                 uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
+                                 const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
+                                 float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
+                                 float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* xyz_s,
+                                 float* image, float* normal_image, float* orient, float* depth, float* weights_sum,
+                                 float* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t sf_ngp_render_shaded_workspace_bytes(uint32_t N, uint32_t T);
+
 /* Fused evaluation render through the occupancy grid (`cuda_ray=True`, eval mode): replaces the host loop
  * `while step < max_steps: march_rays -> network -> composite_rays` of external/nerf/renderer_df.py:543-584 by ONE
  * launch (one ray per lane walks to the end).  `grid` = the density bitfield, C cascades of H^3 cells;

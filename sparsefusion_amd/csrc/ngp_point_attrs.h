@@ -21,12 +21,13 @@ struct NgpPointAttrs { float sigma; float albedo[3]; float grad[3]; float normal
 // torch.clamp(v, -b, b): NaN propagates (fminf / fmaxf alone would return the bound)
 SF_HD float ngp_clamp_sym(float v, float b) { return (v != v) ? v : fminf(fmaxf(v, -b), b); }
 
-// n_eval = 7: everything; n_eval = 1: sigma and albedo only (grad and normal are left untouched)
+// n_eval = 7: everything; n_eval = 1: sigma and albedo only (grad and normal are left untouched); first_eval = 1: the centre is
+// skipped (sigma and albedo are left untouched: the caller already holds that point's values -- k_ngp_shade, ngp_shade.h)
 SF_HD void ngp_point_attrs(const NgpLevels& lv, const float* __restrict__ table, const float* __restrict__ W, float bound,
-                           const float x[3], float eps, int n_eval, NgpPointAttrs& a) {
+                           const float x[3], float eps, int n_eval, NgpPointAttrs& a, int first_eval = 0) {
   float sp = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
 #pragma unroll 1
-  for (int e = 0; e < n_eval; ++e) {
+  for (int e = first_eval; e < n_eval; ++e) {
     // keeps the loop-invariant weight reads (LDS on the GPU) inside the loop: hoisted, they would be pinned in registers and spill
     asm volatile("" ::: "memory");
     const int axis = (e - 1) >> 1;                     // -1 for the centre

@@ -24,6 +24,7 @@
 #include "ngp_bwd_mfma.h"
 #include "ngp_composite_wave.h"
 #include "ngp_scatter_bin.h"
+#include "ngp_shade.h"
 #include <stdlib.h>
 #include <mutex>
 
@@ -413,6 +414,51 @@ extern "C" int sf_ngp_render_forward(const sf_ngp_field* f, const float* rays_o,
       CompositeArgs{z_c, sig_c, rgb_c, z_f, sig_f, rgb_f, nears, fars, N, T, bg_color, z_sorted, sigma_s, rgb_s, image, depth,
                     weights_sum, perm});
   SF_CHECK_LAUNCH("ngp_composite");
+  return SF_OK;
+}
+
+extern "C" uint64_t sf_ngp_render_shaded_workspace_bytes(uint32_t N, uint32_t T) { return sf_ngp_render_forward_workspace_bytes(N, T); }
+
+// Shaded render without gradient (ngp_shade.h).  The albedo forward runs first and unchanged: sample_pdf needs the coarse sigmas
+// before any normal can be placed, and it leaves the sorted ray the two kernels below work on.  Every check comes before the
+// first launch.
+extern "C" int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
+                                            uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
+                                            const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
+                                            float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
+                                            float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* xyz_s,
+                                            float* image, float* normal_image, float* orient, float* depth, float* weights_sum,
+                                            float* workspace, uint64_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!light_d) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: null light_d");
+  if (!isfinite(epsilon) || !(epsilon > 0.0f)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: epsilon must be finite and > 0");
+  if (!isfinite(ambient_ratio)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: ambient_ratio must be finite");
+  if (N == 0) return SF_OK;
+  if (T < 4 || T > 64) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: T must be in [4,64]");
+  if ((uint64_t)N * 2 * T >= (1ull << 32)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: N * 2T must be below 2^32");
+  if (workspace_bytes < sf_ngp_render_shaded_workspace_bytes(N, T)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: workspace too small");
+  if (!lin || !u_fine) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: lin and u_fine tables are required");
+  if (!f || !rays_o || !rays_d || !aabb || !nears || !fars || !z_sorted || !sigma_s || !rgb_s || !normal_s || !rgb_shaded_s || !image ||
+      !depth || !weights_sum || !workspace)
+    SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: null pointer");
+  NgpLevels lv;
+  if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
+  if (int rc = sf_ngp_render_forward(f, rays_o, rays_d, aabb, N, T, min_near, lin, u_coarse, u_fine, u_fine_row_stride, bg_color, nears,
+                                     fars, z_sorted, sigma_s, rgb_s, image, depth, weights_sum, nullptr, workspace, workspace_bytes, stream))
+    return rc;
+  const uint32_t P = N * 2 * T;
+  ShadeArgs s{};
+  s.f = field_ptrs(f); s.lv = lv;
+  s.rays_o = rays_o; s.rays_d = rays_d; s.aabb = aabb; s.z_s = z_sorted; s.rgb_s = rgb_s; s.light_d = light_d;
+  s.P = P; s.T2 = 2 * T; s.ratio = ambient_ratio; s.eps = epsilon;
+  s.normal_s = normal_s; s.rgb_shaded_s = rgb_shaded_s; s.xyz_s = xyz_s;
+  k_ngp_shade<<<sf_grid_cap(sf_div_up(P, 256)), 256, 0, st>>>(s);
+  SF_CHECK_LAUNCH("ngp_shade");
+  // image, depth and weights_sum are written again: the same scan on the same sorted ray (depth and weights_sum come out bit for bit)
+  k_ngp_composite_sorted_wave<<<sf_div_up(N, 4), 256, 0, st>>>(
+      CompositeSortedArgs{z_sorted, sigma_s, rgb_shaded_s, normal_s, rays_d, nears, fars, N, T, bg_color, image, depth, weights_sum,
+                          normal_image, orient});
+  SF_CHECK_LAUNCH("ngp_composite_sorted");
   return SF_OK;
 }
 

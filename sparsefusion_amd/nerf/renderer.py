@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .utils import safe_normalize
 
 
 def get_default_torch_ngp_opt():
@@ -276,20 +277,49 @@ class NeRFRenderer(nn.Module):
 
     def run(self, rays_o, rays_d, num_steps=128, upsample_steps=128, light_d=None, ambient_ratio=1.0,
             shading='albedo', bg_color=None, perturb=False, fixed_light=False, noise=None, **kwargs):
-        """rays_o, rays_d: [B, N, 3] (B == 1).  `noise` = dict(u_coarse=[N,T], u_fine=[N,T]) injects the draws."""
-        if shading != 'albedo':
-            raise NotImplementedError("only shading='albedo' is on the distillation path (distillation.py:209,282)")
+        """rays_o, rays_d: [B, N, 3] (B == 1).  `noise` = dict(u_coarse=[N,T], u_fine=[N,T]) injects the draws.
+
+        shading='albedo': the differentiable fused render.  shading='lambertian' (renderer_df.py:404-456): the same samples, then per
+        sorted sample the finite-difference normal (epsilon 1e-2, the reference's) and albedo * (ambient_ratio + (1 - ambient_ratio)
+        * max(n . -light_d, 0)), composited -- one no-gradient entry (sf_ngp_render_shaded_forward), so it is allowed when grad mode
+        is off or no field parameter requires grad, and raises otherwise.  `light_d`: any 3-vector; None draws
+        safe_normalize(rays_o[0] + randn(3)) (the draw an albedo render consumes at the same place) or, with fixed_light, the
+        reference's rotation of rays_o[0] (:345-348).  The result then also holds 'loss_orient' (mean over all N * 2T samples of
+        w * max(n . d, 0)^2, the reference's) and 'normal' [..., 3] = sum w n, the normal image -- an extension: the reference
+        returns no such key.  'loss_smooth' is NOT returned: the reference compares with normals at torch.randn_like-perturbed
+        points, a random stream this library does not reproduce.  'textureless' and 'normal' raise: the reference shades them
+        with its random smooth normal (NeRFNetwork.normal(smooth=True))."""
+        if shading not in ('albedo', 'lambertian'):
+            raise NotImplementedError(f"shading={shading!r}: only 'albedo' and 'lambertian' are rendered ('textureless' and 'normal' use "
+                                      "the reference's random smooth normal, common_forward_smooth, which is not reproduced)")
         if num_steps != upsample_steps:
             raise NotImplementedError("the fused render needs num_steps == upsample_steps (reference: 64/64)")
+        shaded = shading == 'lambertian'
+        if shaded and torch.is_grad_enabled() and any(q.requires_grad for q in self._field_params()):
+            raise NotImplementedError("the shaded render has no backward: call it under torch.no_grad() or with a frozen field "
+                                      "(shading='albedo' is the differentiable render)")
+        if shaded and light_d is not None:
+            light_d = torch.as_tensor(light_d)
+            if light_d.numel() != 3:
+                raise ValueError("light_d must be a 3-vector")
         prefix = rays_o.shape[:-1]
         o = rays_o.contiguous().view(-1, 3).float()
         d = rays_d.contiguous().view(-1, 3).float()
         N, T, dev = o.shape[0], int(num_steps), o.device
         aabb = self.aabb_train if self.training else self.aabb_infer
         lin, det = self._table(T, dev)
+        if shaded and light_d is not None:
+            light = light_d.detach().reshape(3).to(device=dev, dtype=torch.float32)
+        elif shaded and fixed_light:
+            rot_m = torch.tensor([[0.63, .65, -0.43], [-.43, .75, -0.5], [-.65, .13, .75]], device=dev, dtype=torch.float)
+            light = safe_normalize(o[0] @ rot_m)                    # renderer_df.py:345-349
+        else:
+            light = None
+        if light_d is None and not fixed_light and (noise is None or shaded):
+            draw = torch.randn(3, device=dev, dtype=torch.float)       # (:351) the light of a shaded render; consumed, unused for 'albedo'
+            if shaded:
+                light = safe_normalize(o[0] + draw)
         if noise is None:
-            if light_d is None and not fixed_light:
-                torch.randn(3, device=dev, dtype=torch.float)          # consumed, unused for 'albedo' (:351)
             u_coarse = torch.rand(N, T, device=dev) if perturb else None   # :363
             u_fine = torch.rand(N, T, device=dev) if self.training else None  # sample_pdf det=not training (:31)
         else:
@@ -301,11 +331,39 @@ class NeRFRenderer(nn.Module):
             bg_color = 1
         if torch.is_tensor(bg_color):
             raise NotImplementedError("per-ray bg_color tensors are not on the distillation path (bg_color=0)")
+        if shaded:
+            return self._run_shaded(prefix, o, d, aabb, T, lin, u_coarse, u_f, stride, float(bg_color), light.contiguous(),
+                                    float(ambient_ratio))
         image, weights_sum, depth, nears, fars = _RenderFn.apply(
             self._field_handle(), o, d, aabb, T, self.min_near, lin, u_coarse, u_f, stride, float(bg_color),
             self._rays_per_row(N, kwargs), torch.is_grad_enabled(), *self._field_params())
         return {'image': image.view(*prefix, 3), 'depth': depth.view(*prefix), 'weights_sum': weights_sum,
                 'mask': (nears < fars).view(*prefix)}
+
+    @torch.no_grad()
+    def _run_shaded(self, prefix, o, d, aabb, T, lin, u_coarse, u_fine, u_stride, bg, light, ratio, epsilon=1e-2):
+        """One sf_ngp_render_shaded_forward call (csrc/ngp_shade.h); `light` [3] stays on the device."""
+        params = [q.detach().contiguous() for q in self._field_params()]
+        _lib.require_cuda(o, d, aabb, light, *params)
+        N, dev = o.shape[0], o.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        nears, fars = torch.empty(N, **f32), torch.empty(N, **f32)
+        z_s, sig_s = torch.empty(N, 2 * T, **f32), torch.empty(N, 2 * T, **f32)
+        rgb_s, nrm_s, col_s = (torch.empty(N, 2 * T, 3, **f32) for _ in range(3))
+        image, nimg = torch.empty(N, 3, **f32), torch.empty(N, 3, **f32)
+        depth, ws, orient = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, **f32)
+        lib = _lib.lib()
+        wbytes = lib.sf_ngp_render_shaded_workspace_bytes(N, T)
+        work = torch.empty(max(1, wbytes // 4), **f32)
+        f = self._field_handle().struct(params)
+        rc = lib.sf_ngp_render_shaded_forward(C.byref(f), _lib.ptr(o), _lib.ptr(d), _lib.ptr(aabb), N, T, float(self.min_near),
+                                              _lib.ptr(lin), _lib.ptr(u_coarse), _lib.ptr(u_fine), int(u_stride), bg, _lib.ptr(light),
+                                              ratio, float(epsilon), _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(z_s), _lib.ptr(sig_s),
+                                              _lib.ptr(rgb_s), _lib.ptr(nrm_s), _lib.ptr(col_s), None, _lib.ptr(image), _lib.ptr(nimg),
+                                              _lib.ptr(orient), _lib.ptr(depth), _lib.ptr(ws), _lib.ptr(work), wbytes, _lib.stream_ptr())
+        _lib.check(rc, "ngp_render_shaded_forward")
+        return {'image': image.view(*prefix, 3), 'depth': depth.view(*prefix), 'weights_sum': ws, 'mask': (nears < fars).view(*prefix),
+                'loss_orient': orient.sum() / max(1, N * 2 * T), 'normal': nimg.view(*prefix, 3)}
 
     @staticmethod
     def _rays_per_row(N, kwargs):
@@ -388,6 +446,7 @@ class NeRFRenderer(nn.Module):
         dev = rays_o.device
         depth, image = torch.empty((B, N), device=dev), torch.empty((B, N, 3), device=dev)
         weights_sum = torch.empty((B, N), device=dev)
+        normal = None
         for b in range(B):
             for head in range(0, N, max_ray_batch):
                 tail = min(head + max_ray_batch, N)
@@ -395,7 +454,14 @@ class NeRFRenderer(nn.Module):
                 depth[b:b + 1, head:tail] = r['depth']
                 weights_sum[b:b + 1, head:tail] = r['weights_sum']
                 image[b:b + 1, head:tail] = r['image']
-        return {'depth': depth, 'image': image, 'weights_sum': weights_sum}
+                if 'normal' in r:                               # shaded chunks (run, shading='lambertian'): the normal map
+                    if normal is None:
+                        normal = torch.empty((B, N, 3), device=dev)
+                    normal[b:b + 1, head:tail] = r['normal']
+        out = {'depth': depth, 'image': image, 'weights_sum': weights_sum}
+        if normal is not None:
+            out['normal'] = normal
+        return out
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
         """renderer_df.py:643-679: one `run` over all rays, or chunks of max_ray_batch when staged."""

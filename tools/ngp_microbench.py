@@ -1,4 +1,7 @@
-"""Time the fused NGP render (forward, forward+backward) at the BASELINE size: 128x128 rays, 64+64 samples."""
+"""Time the fused NGP render (forward, forward+backward) at the BASELINE size: 128x128 rays, 64+64 samples.
+--shading lambertian adds, after the default output: the shaded render (sf_ngp_render_shaded_forward), the albedo forward at the same
+size, and the composed route (albedo forward + sf_ngp_point_attrs over the sorted points + torch glue for the weights and the sums),
+each the median of 5 torch-event timings after a warm-up."""
 import os
 import sys
 import time
@@ -35,3 +38,66 @@ def run(backward, iters):
 run(True, 3)
 print(f"render fwd      : {run(False, 20):.3f} ms")
 print(f"render fwd+bwd  : {run(True, 20):.3f} ms")
+
+
+def shaded_times():
+    import ctypes as C
+    from sparsefusion_amd import _lib, mesh
+    light = torch.tensor([0.3, -0.5, 0.81], device=dev)
+    light = light / light.norm()
+    ratio, T = 0.1, net.opt.num_steps
+    of, df = o[0].contiguous(), d[0].contiguous()
+    N = of.shape[0]
+    skw = dict(kw, perturb=False)
+
+    def shaded():
+        return net.render(o, d, **dict(skw, shading='lambertian', light_d=light, ambient_ratio=ratio))
+
+    def albedo():
+        return net.render(o, d, **skw)
+
+    def composed():
+        # the albedo forward through the C ABI (the sorted ray is not part of run's result), then the point attributes and torch
+        f32 = dict(dtype=torch.float32, device=dev)
+        lin, det = net._table(T, of.device)
+        params = [q.detach().contiguous() for q in net._field_params()]
+        f = net._field_handle().struct(params)
+        lib = _lib.lib()
+        nears, fars, depth, ws = (torch.empty(N, **f32) for _ in range(4))
+        z_s, sig_s, rgb_s, image = torch.empty(N, 2 * T, **f32), torch.empty(N, 2 * T, **f32), torch.empty(N, 2 * T, 3, **f32), torch.empty(N, 3, **f32)
+        wbytes = lib.sf_ngp_render_forward_workspace_bytes(N, T)
+        work = torch.empty(wbytes // 4, **f32)
+        u_fine = torch.rand(N, T, device=dev)                          # train mode: the inverse-CDF draw
+        _lib.check(lib.sf_ngp_render_forward(C.byref(f), _lib.ptr(of), _lib.ptr(df), _lib.ptr(net.aabb_train), N, T, float(net.min_near),
+                                             _lib.ptr(lin), None, _lib.ptr(u_fine), T, 0.0, _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(z_s),
+                                             _lib.ptr(sig_s), _lib.ptr(rgb_s), _lib.ptr(image), _lib.ptr(depth), _lib.ptr(ws), None,
+                                             _lib.ptr(work), wbytes, _lib.stream_ptr()), "ngp_render_forward")
+        x = torch.min(torch.max(of[:, None] + df[:, None] * z_s[..., None], net.aabb_train[:3]), net.aabb_train[3:])
+        n = mesh.point_attributes(net, x.view(-1, 3), 1e-2, sigma=False, albedo=False, grad=False)["normal"].view(N, 2 * T, 3)
+        col = rgb_s * (ratio + (1 - ratio) * (n @ -light).clamp(min=0)).unsqueeze(-1)
+        deltas = torch.cat([z_s[:, 1:] - z_s[:, :-1], ((fars - nears) / T)[:, None]], -1)
+        alphas = 1 - torch.exp(-deltas * sig_s)
+        w = alphas * torch.cumprod(torch.cat([torch.ones_like(alphas[:, :1]), 1 - alphas + 1e-15], -1), -1)[:, :-1]
+        img = (w[..., None] * col).sum(-2) + (1 - w.sum(-1))[:, None] * 0.0
+        return img, (w[..., None] * n).sum(-2), (w * (n * df[:, None]).sum(-1).clamp(min=0) ** 2).mean()
+
+    def median_ms(fn):
+        with torch.no_grad():
+            fn()
+            ts = []
+            for _ in range(5):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b))
+        return sorted(ts)[2]
+
+    print(f"shaded render   : {median_ms(shaded):.3f} ms")
+    print(f"albedo forward  : {median_ms(albedo):.3f} ms")
+    print(f"composed shaded : {median_ms(composed):.3f} ms")
+
+
+if "--shading" in sys.argv and sys.argv[sys.argv.index("--shading") + 1:][:1] == ["lambertian"]:
+    shaded_times()
