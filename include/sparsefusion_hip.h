@@ -193,6 +193,18 @@ int sf_ngp_density_lattice(const sf_ngp_field* f, const float* ax, const float* 
 int sf_ngp_point_attrs(const sf_ngp_field* f, const float* xyz, uint32_t P, float epsilon,
                        float* sigma, float* albedo, float* grad, float* normal, void* stream);
 
+/* Texture atlas of a triangle mesh baked from the field (the reference's _export, renderer_df.py:166-306, without xatlas /
+ * nvdiffrast: one right-angled chart per triangle, closed-form UVs; layout and texel -> point rule in csrc/ngp_texture.h and
+ * DESIGN.md section 9.3).  verts [V,3] f32 world coordinates, faces [F,3] i32, texture W x W, texel t = y * W + x with its centre
+ * at (u, v_atlas) = ((x + 0.5) / W, (y + 0.5) / W).  Outputs, each may be NULL (not written), at least one required:
+ * rgb8 [W*W*3] u8 = (uint8)(min(max(albedo, 0), 1) * 255) (truncation, NaN -> 0); albedo [W*W,3] f32, bit-identical to
+ * sf_ngp_density on the texel's point; xyz [W*W,3] f32, that point; face_id [W*W] i32.  A texel of no face, or of a face with a
+ * vertex index outside [0, V), is written as 0 / 0 / 0 / -1 and costs no field evaluation.  SF_ERR_INVALID, before any device
+ * call: NULL f / verts / faces, all outputs NULL, W == 0, W * W >= 2^31, cell edge W / ceil(sqrt(ceil(F / 2))) < 6 (the message
+ * names the smallest W).  F == 0: every texel is written as unused. */
+int sf_ngp_texture_bake(const sf_ngp_field* f, const float* verts, uint32_t V, const int32_t* faces, uint32_t F, uint32_t W,
+                        uint8_t* rgb8, float* albedo, float* xyz, int32_t* face_id, void* stream);
+
 /* Separable Gaussian of scipy.ndimage.gaussian_filter (mode 'reflect', radius int(truncate*sigma + 0.5) <= 64, taps in
  * double, one pass per axis in the order 0, 1, 2, each output rounded to f32).  in and out must not alias.  stats (or NULL)
  * receives {mean, population std} of out in double, reduced in a fixed order (bit-reproducible).

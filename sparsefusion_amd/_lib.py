@@ -92,6 +92,8 @@ SIGNATURES = {
     "sf_ngp_density": (C.c_int, [C.POINTER(SfNgpField), c_f32p, u32, c_f32p, c_f32p, C.c_void_p]),
     "sf_ngp_density_lattice": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, u32, u32, u32, c_f32p, C.c_void_p]),
     "sf_ngp_point_attrs": (C.c_int, [C.POINTER(SfNgpField), c_f32p, u32, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "sf_ngp_texture_bake": (C.c_int, [C.POINTER(SfNgpField), c_f32p, u32, c_i32p, u32, u32, C.c_void_p, c_f32p, c_f32p, c_i32p,
+                                      C.c_void_p]),
     "sf_gaussian3d_workspace_bytes": (u64, [u32, u32, u32]),
     "sf_gaussian3d": (C.c_int, [c_f32p, c_f32p, u32, u32, u32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, u64, C.c_void_p]),
     "sf_mc_workspace_bytes": (u64, [u32, u32, u32]),

@@ -1,10 +1,12 @@
 // Mesh export (NeRFRenderer.export_mesh, external/nerf/renderer_df.py:122-165; extract_fields / extract_geometry,
 // external/nerf/utils.py:174-204): the NGP density on a lattice, the separable Gaussian + volume statistics and marching cubes
-// of mesh_kernels.h.  Host entry points declared in include/sparsefusion_hip.h.  See DESIGN.md section 9.
+// of mesh_kernels.h, the point attributes of ngp_point_attrs.h and the texture bake of ngp_texture.h (the reference's _export,
+// renderer_df.py:166-306).  Host entry points declared in include/sparsefusion_hip.h.  See DESIGN.md section 9.
 #include "sf_common.h"
 #include "mesh_kernels.h"
 #include "ngp_field_lds.h"
 #include "ngp_point_attrs.h"
+#include "ngp_texture.h"
 
 // sigma at (ax[i], ay[j], az[k]) -> sigma[(i * ny + j) * nz + k], straight from the lattice index (no point buffer).  The per-point
 // code is k_ngp_field's (ngp_render.hip): weights in LDS, the same encode / MLP / activation, so a lattice value is bit-identical
@@ -85,6 +87,43 @@ extern "C" int sf_ngp_point_attrs(const sf_ngp_field* f, const float* xyz, uint3
   if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
   k_ngp_point_attrs<<<sf_grid_cap(sf_div_up(P, 256)), 256, 0, st>>>(sf_ngp_field_ptrs(f), lv, xyz, P, epsilon, sigma, albedo, grad, normal);
   SF_CHECK_LAUNCH("ngp_point_attrs");
+  return SF_OK;
+}
+
+// Texture atlas of a mesh baked from the field (ngp_texture.h): one thread per texel -- its face and clamped barycentrics from the
+// texel index, the point on the face, one evaluation of the field (bit-identical to sf_ngp_density on that fp32 point), the stores.
+// Launch shape, LDS weights and the barrier at the top of each round as k_ngp_lattice.  Null outputs are skipped.
+__global__ __launch_bounds__(256) void k_ngp_texture_bake(FieldPtrs f, NgpLevels lv, NgpAtlas at, const float* __restrict__ verts,
+                                                          uint32_t V, const int32_t* __restrict__ faces, uint32_t F, NgpTexOut o) {
+  __shared__ __attribute__((aligned(16))) float W[NGP_WTOTAL];
+  load_weights_lds(W, f);
+  const uint64_t P = (uint64_t)at.W * at.W;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < P; base += (uint64_t)gridDim.x * blockDim.x) {
+    __syncthreads();
+    const uint64_t t = base + threadIdx.x;
+    if (t >= P) continue;
+    ngp_texture_texel(lv, f.table, W, f.bound, at, verts, V, faces, F, (uint32_t)t, o);
+  }
+}
+
+extern "C" int sf_ngp_texture_bake(const sf_ngp_field* f, const float* verts, uint32_t V, const int32_t* faces, uint32_t F, uint32_t W,
+                                   uint8_t* rgb8, float* albedo, float* xyz, int32_t* face_id, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!f || !verts || !faces) SF_FAIL(SF_ERR_INVALID, "ngp_texture_bake: null field, vertices or faces");
+  if (!rgb8 && !albedo && !xyz && !face_id) SF_FAIL(SF_ERR_INVALID, "ngp_texture_bake: at least one output is required");
+  NgpAtlas at;
+  switch (ngp_atlas_make(F, W, &at)) {
+    case 1: SF_FAIL(SF_ERR_INVALID, "ngp_texture_bake: W must be >= 1");
+    case 2: SF_FAIL(SF_ERR_INVALID, "ngp_texture_bake: need W * W < 2^31");
+    case 3: SF_FAIL(SF_ERR_INVALID, "ngp_texture_bake: %u faces in a %u x %u texture leave cells of %u texels, below 6: the smallest W is %u",
+                    F, W, W, at.c, 6 * at.G);
+    default: break;
+  }
+  NgpLevels lv;
+  if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
+  k_ngp_texture_bake<<<sf_grid_cap(sf_div_up((uint64_t)W * W, 256)), 256, 0, st>>>(sf_ngp_field_ptrs(f), lv, at, verts, V, faces, F,
+                                                                                 NgpTexOut{rgb8, albedo, xyz, face_id});
+  SF_CHECK_LAUNCH("ngp_texture_bake");
   return SF_OK;
 }
 

@@ -1,6 +1,7 @@
 """Mesh export on the GPU: the NGP density on a lattice, PyMCubes' Gaussian smoothing, fp64 volume statistics and marching cubes
 (C ABI in include/sparsefusion_hip.h, kernels in csrc/mesh_kernels.h and csrc/mesh.hip), and per-vertex
-colour and normal from the field (sf_ngp_point_attrs, csrc/ngp_point_attrs.h) with OBJ / PLY writers that carry them.
+colour and normal from the field (sf_ngp_point_attrs, csrc/ngp_point_attrs.h) with OBJ / PLY writers that carry them, and a
+texture atlas baked from the field (sf_ngp_texture_bake, csrc/ngp_texture.h) with its OBJ / MTL / PNG writers.
 
 The functions take and return device tensors; numpy input is run on the current HIP device and comes back as numpy, as a `mcubes`
 user would expect.  There is no CPU path.
@@ -253,3 +254,137 @@ def export_ply(vertices, faces, filename, colors=None, normals=None):
         fh.write(ply_header(v.shape[0], f.shape[0], c is not None, n is not None).encode("ascii"))
         fh.write(rec.tobytes())
         fh.write(frec.tobytes())
+
+
+# ------------------------------------------------------------------------------------------------------------------ texture atlas
+# One right-angled chart per triangle, two charts per square cell: the layout of csrc/ngp_texture.h, restated.
+ATLAS_MIN_CELL = 6
+
+MTL_TEXT = ("newmtl mat0 \n"
+            "Ka 1.000000 1.000000 1.000000 \n"
+            "Kd 1.000000 1.000000 1.000000 \n"
+            "Ks 0.000000 0.000000 0.000000 \n"
+            "Tr 1.000000 \n"
+            "illum 1 \n"
+            "Ns 0.000000 \n"
+            "map_Kd albedo.png \n")           # what renderer_df.py:298-306 writes (name = ''), trailing blanks included
+
+
+def atlas_layout(F, W):
+    """(G, c) of F faces in a W x W texture: faces are paired into G x G square cells of edge c = W // G texels,
+    G = ceil(sqrt(ceil(F / 2))); face f is half f & 1 of cell f >> 1 at (row, col) = divmod(f >> 1, G).  F == 0 -> (0, 0).
+    ValueError if c < 6 (a chart needs a leg of at least one texel, a margin and a gutter), naming the smallest W that works."""
+    F, W = int(F), int(W)
+    if F < 0 or W < 1:
+        raise ValueError(f"atlas_layout: need F >= 0 and W >= 1, got F={F}, W={W}")
+    if W * W >= 1 << 31:
+        raise ValueError(f"atlas_layout: need W * W < 2^31, got W={W}")
+    if F == 0:
+        return 0, 0
+    cells = (F + 1) // 2
+    G = 1
+    while G * G < cells:
+        G += 1
+    c = W // G
+    if c < ATLAS_MIN_CELL:
+        raise ValueError(f"atlas_layout: {F} faces in a {W} x {W} texture leave cells of {c} texels, below {ATLAS_MIN_CELL}: "
+                         f"the smallest W is {ATLAS_MIN_CELL * G}")
+    return G, c
+
+
+def atlas_uv(F, W):
+    """uv [F, 3, 2] float32, (u, v_atlas) of face corner 0 / 1 / 2: texel centres, (x + 0.5) / W with the division in float32.
+    In cell-local texel indices and with leg l = c - 5 the lower half's corners are (1, 1), (1 + l, 1), (1, 1 + l) and the upper
+    half's (c - 2, c - 2), (c - 2 - l, c - 2), (c - 2, c - 2 - l): the same winding.  Image row y holds v_atlas = (y + 0.5) / W, so a
+    `vt` line carries 1 - v_atlas."""
+    G, c = atlas_layout(F, W)
+    f = np.arange(int(F), dtype=np.int64)
+    if f.size == 0:
+        return np.zeros((0, 3, 2), dtype=np.float32)
+    q, half = f >> 1, f & 1
+    row, col = q // G, q % G
+    leg = c - 5
+    ij = np.array([[1, 1], [1 + leg, 1], [1, 1 + leg]], dtype=np.int64)[None]                   # [1, 3, 2] (i, j), lower half
+    ij = np.where(half[:, None, None] == 1, c - 1 - ij, ij)
+    xy = ij + np.stack([col, row], -1)[:, None, :] * c
+    return ((xy.astype(np.float32) + np.float32(0.5)) / np.float32(W)).astype(np.float32)
+
+
+@torch.no_grad()
+def bake_texture(net, vertices_world, faces, W, rgb8=True, albedo=False, xyz=False, face_id=False):
+    """One launch of sf_ngp_texture_bake: the field's albedo at every texel of the atlas of atlas_layout(F, W).  vertices_world
+    [V, 3] float32 and faces [F, 3] int32 are device tensors.  Returns a dict of the requested outputs among rgb8 [W, W, 3] uint8
+    (truncation of clip(albedo, 0, 1) * 255, NaN -> 0), albedo [W, W, 3] float32 (bit-identical to net.density on the texel's
+    point), xyz [W, W, 3] float32 (that point) and face_id [W, W] int32; row y, column x is the texel with its centre at
+    (u, v_atlas) = ((x + 0.5) / W, (y + 0.5) / W).  A texel of no face, or of a face with a vertex index outside [0, V), holds
+    0 / 0 / 0 / -1.  Every texel is a direct sample of the field: no supersampling, nothing to inpaint."""
+    params = [p.detach().contiguous() for p in net._field_params()]
+    _lib.require_cuda(vertices_world, faces, *params)
+    if not (rgb8 or albedo or xyz or face_id):
+        raise ValueError("bake_texture: at least one output is required")
+    v = vertices_world.detach().reshape(-1, 3).float().contiguous()
+    fc = faces.detach().reshape(-1, 3).to(torch.int32).contiguous()
+    V, F, W = v.shape[0], fc.shape[0], int(W)
+    atlas_layout(F, W)
+    dev = v.device
+    out = {}
+    if rgb8:
+        out["rgb8"] = torch.empty(W, W, 3, dtype=torch.uint8, device=dev)
+    for name, want in (("albedo", albedo), ("xyz", xyz)):
+        if want:
+            out[name] = torch.empty(W, W, 3, dtype=torch.float32, device=dev)
+    if face_id:
+        out["face_id"] = torch.empty(W, W, dtype=torch.int32, device=dev)
+    keep_v, keep_f = torch.zeros(1, 3, device=dev), torch.zeros(1, 3, dtype=torch.int32, device=dev)      # valid pointers for an empty mesh
+    f = net._field_handle().struct(params)
+    rc = _lib.lib().sf_ngp_texture_bake(C.byref(f), _lib.ptr(v if V else keep_v), V, _lib.ptr(fc if F else keep_f), F, W,
+                                        _lib.ptr(out.get("rgb8")), _lib.ptr(out.get("albedo")), _lib.ptr(out.get("xyz")),
+                                        _lib.ptr(out.get("face_id")), _lib.stream_ptr())
+    _lib.check(rc, "ngp_texture_bake")
+    return out
+
+
+def write_png(path, rgb8):
+    """8-bit RGB PNG of rgb8 [H, W, 3] uint8 (numpy or tensor), row 0 at the top: signature, IHDR, one IDAT (filter 0 on every
+    row, zlib), IEND -- the standard library only."""
+    import struct
+    import zlib
+    a = rgb8.detach().cpu().numpy() if isinstance(rgb8, torch.Tensor) else np.asarray(rgb8)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"write_png: expected uint8 [H, W, 3], got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), dtype=np.uint8)                   # byte 0 of a row: filter type 0 (none)
+    rows[:, 1:] = a.reshape(h, 3 * w)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+                 chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def export_obj_textured(vertices, faces, uvs, filename, mtl_name, normals=None):
+    """Textured OBJ: `mtllib <mtl_name>`, one `v x y z` per vertex, `vt u (1 - v_atlas)` for uvs [F, 3, 2] (3 F lines, corner k of
+    face f is line 3 f + k), optional `vn x y z` per vertex, `usemtl mat0`, then `f a/ta b/tb c/tc` (`a/ta/a ..` with normals),
+    1-based.  Coordinates and uvs are printed with 9 significant digits, which parse back to the same float32; 1 - v_atlas is taken
+    in float32.  One C-level format per block of lines, as export_obj."""
+    v, f, _, n = _mesh_arrays(vertices, faces, None, normals, "export_obj_textured")
+    uv = uvs.detach().cpu().numpy() if isinstance(uvs, torch.Tensor) else np.asarray(uvs)
+    uv = np.ascontiguousarray(uv, dtype=np.float32)
+    if uv.shape != (f.shape[0], 3, 2):
+        raise ValueError(f"export_obj_textured: uvs have shape {uv.shape} for {f.shape[0]} faces, expected [F, 3, 2]")
+    vt = np.stack([uv[..., 0], np.float32(1.0) - uv[..., 1]], -1).astype(np.float32).reshape(-1, 2)
+    f = f + 1
+    ti = np.arange(1, 3 * f.shape[0] + 1, dtype=np.int64).reshape(-1, 3)
+    with open(filename, "w") as fh:
+        fh.write(f"mtllib {mtl_name}\n")
+        fh.write(("v %.9g %.9g %.9g\n" * v.shape[0]) % tuple(v.astype(np.float64).ravel().tolist()))
+        fh.write(("vt %.9g %.9g\n" * vt.shape[0]) % tuple(vt.astype(np.float64).ravel().tolist()))
+        if n is not None:
+            fh.write(("vn %.9g %.9g %.9g\n" * n.shape[0]) % tuple(n.astype(np.float64).ravel().tolist()))
+        fh.write("usemtl mat0\n")
+        if n is None:
+            fh.write(("f %d/%d %d/%d %d/%d\n" * f.shape[0]) % tuple(np.stack([f, ti], -1).ravel().tolist()))
+        else:
+            fh.write(("f %d/%d/%d %d/%d/%d %d/%d/%d\n" * f.shape[0]) % tuple(np.stack([f, ti, f], -1).ravel().tolist()))

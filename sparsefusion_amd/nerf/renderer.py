@@ -212,16 +212,47 @@ class NeRFRenderer(nn.Module):
         R = 128 if resolution is None else int(resolution)
         return self._export_mesh(path, resolution, 2.0 * self.bound / (R - 1) if epsilon is None else epsilon)
 
-    def _export_mesh(self, path, resolution, epsilon):
-        """epsilon None: geometry only (export_mesh); else also vertex attributes and the PLY file"""
+    @torch.no_grad()
+    def export_mesh_textured(self, path, resolution=None, S=128, texture_size=2048, normals=True):
+        """export_mesh with the deliverable the reference's `_export` is written around (renderer_df.py:166-306, commented out
+        there): `path/mesh.obj` (world coordinates, `vt` per face corner, `vn` with `normals`), `path/mesh.mtl` and
+        `path/albedo.png`, a texture_size x texture_size atlas baked from the field in one launch (mesh.bake_texture).  The same
+        lattice, smoothing, level and marching cubes as export_mesh: vertices and faces are bit-identical to its.  Returns
+        (vertices [V, 3], faces [F, 3], uvs [F, 3, 2] float32 (u, v_atlas) on the field's device, texture [W, W, 3] uint8).
+
+        In place of xatlas and a rasteriser every triangle gets a right-angled chart of its own (mesh.atlas_uv): every texel is a
+        direct sample of the field on its face, so there is no `ssaa` argument and nothing to inpaint.  With `normals` the `vn`
+        lines are the outward normals of export_mesh_attributes at one lattice spacing.  ValueError if texture_size leaves a
+        chart cell under 6 texels."""
         from .. import mesh
         R = 128 if resolution is None else int(resolution)
+        vertices, faces, world = self._mesh_geometry(R)
+        W = int(texture_size)
+        uvs = mesh.atlas_uv(faces.shape[0], W)
+        texture = mesh.bake_texture(self, world, faces, W)["rgb8"]
+        vn = mesh.vertex_attributes(self, world, 2.0 * self.bound / (R - 1))[1] if normals else None
+        os.makedirs(path, exist_ok=True)
+        mesh.export_obj_textured(world, faces, uvs, os.path.join(path, 'mesh.obj'), 'mesh.mtl', normals=vn)
+        with open(os.path.join(path, 'mesh.mtl'), 'w') as fh:
+            fh.write(mesh.MTL_TEXT)
+        mesh.write_png(os.path.join(path, 'albedo.png'), texture)
+        return world, faces, torch.from_numpy(uvs).to(world.device), texture
+
+    def _mesh_geometry(self, R):
+        """(vertices in index coordinates, faces, vertices in world coordinates) of the R^3 lattice"""
+        from .. import mesh
         sigmas = mesh.density_lattice(self, R, self.bound)
         smooth, stats = mesh.smooth_gaussian(sigmas, sigma=1.5, return_stats=True)
         mean, std = (float(x) for x in stats.cpu())
         vertices, faces = mesh.marching_cubes(smooth, mean + std * 0.25)
+        return vertices, faces, vertices / (R - 1.0) * (2 * self.bound) - self.bound
+
+    def _export_mesh(self, path, resolution, epsilon):
+        """epsilon None: geometry only (export_mesh); else also vertex attributes and the PLY file"""
+        from .. import mesh
+        R = 128 if resolution is None else int(resolution)
+        vertices, faces, world = self._mesh_geometry(R)
         os.makedirs(path, exist_ok=True)
-        world = vertices / (R - 1.0) * (2 * self.bound) - self.bound
         if epsilon is None:
             mesh.export_obj(vertices, faces, os.path.join(path, 'mcubes_mesh.obj'))
             return world, faces

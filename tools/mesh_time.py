@@ -2,10 +2,13 @@
 next to the CPU pipeline it is tested against (scipy gaussian_filter + numpy level + tests/mesh_ref.py marching cubes) on the
 same field.  One JSON line per resolution.
 
-    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu] [--attrs]
+    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu] [--attrs] [--texture]
 
 --attrs adds, per resolution and for a fixed set of 2^20 random points, the one-launch vertex attributes (sf_ngp_point_attrs) next to
 the same quantities composed from seven sf_ngp_density calls and torch glue (what the field API offered before that entry point).
+
+--texture adds, per resolution, the one-launch texture bake of the exported mesh (sf_ngp_texture_bake, 8-bit output) at 1024^2 and
+2048^2 next to the composed route: a point buffer built by torch from the atlas layout, sf_ngp_density on it, torch quantisation.
 """
 import argparse
 import json
@@ -104,12 +107,45 @@ def attrs_time(net, x, eps, reps):
                 seven_density_calls_ms=_median_ms(composed, reps))
 
 
+def texture_time(net, verts, faces, W, reps):
+    """ms of one sf_ngp_texture_bake launch (rgb8 only) and of the composed route on the same mesh.  The texel -> (face, barycentric
+    numerators) table of the composed route depends on (F, W) alone and is built once, outside the timing."""
+    import texture_common as tc
+    F = int(faces.shape[0])
+    G, c = mesh.atlas_layout(F, W)
+    dev = verts.device
+    face_id, _ = tc.np_bake_points(np.zeros((1, 3), np.float32), np.zeros((F, 3), np.int64), W)
+    used = torch.from_numpy(face_id.reshape(-1) >= 0).to(dev)
+    fid = torch.from_numpy(face_id.reshape(-1).astype(np.int64)).to(dev)[used]
+    t = torch.nonzero(used).squeeze(1)
+    x, y = t % W, t // W
+    i, j = x % c, y % c
+    upper = (fid & 1) == 1
+    i, j = torch.where(upper, c - 1 - i, i), torch.where(upper, c - 1 - j, j)
+    leg = c - 5
+    p, q = (i - 1).clamp(0, leg), (j - 1).clamp(0, leg)
+    e = (p + q - leg).clamp(min=0)
+    u, v = ((p - (e + 1) // 2).float() / leg)[:, None], ((q - e // 2).float() / leg)[:, None]
+
+    def composed():
+        tri = verts[faces.long()[fid]]                                # [n, 3, 3]
+        pts = ((1.0 - u) - v) * tri[:, 0] + u * tri[:, 1] + v * tri[:, 2]
+        a = net.density(pts)["albedo"]
+        img = torch.zeros(W * W, 3, dtype=torch.uint8, device=dev)
+        img[used] = (a.clamp(0, 1) * 255).to(torch.uint8)
+        return img.view(W, W, 3)
+
+    return dict(W=W, F=F, cell=c, texels_used=int(used.sum()), one_launch_ms=_median_ms(lambda: mesh.bake_texture(net, verts, faces, W), reps),
+                composed_ms=_median_ms(composed, reps))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, nargs="+", default=[128, 256])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--attrs", action="store_true")
+    ap.add_argument("--texture", action="store_true")
     a = ap.parse_args()
     golden = torch.load(os.path.join(ROOT, "tests", "golden", "ngp_render.pt"))
     p = params_from_cfg(golden["teacher"]["cfg"])
@@ -144,6 +180,10 @@ def main():
                 rand = ((torch.rand(1 << 20, 3, generator=g) * 2 - 1) * BOUND).to(verts.device)
                 out["attrs_vertices"] = attrs_time(net, verts.contiguous(), eps, a.reps)
                 out["attrs_random"] = attrs_time(net, rand, eps, a.reps)
+        if a.texture:
+            with torch.no_grad():
+                verts, faces = net.export_mesh(tmp, resolution=R)
+                out["texture"] = [texture_time(net, verts.contiguous(), faces, W, a.reps) for W in (1024, 2048)]
         if not a.no_cpu:
             v = vol.cpu().numpy()
             t0 = time.perf_counter()
