@@ -97,6 +97,65 @@ extern "C" void emu_field_bwd(const float* table, const int32_t* h_offsets, uint
   }
 }
 
+// ---- the per-element float64 checks of tests/ngp_bwd_cases.py: the features ngp_encode gives every point (the values the kernel's re-gather
+// loop computes, and what a field cache holds), and the kernel launched chunk by chunk the way sf_ngp_render_backward does -- ray / sample
+// pointers offset to the chunk, d(feat) in the layout of the whole set (dfeat_P, p_off), one thr for all launches, any grid per chunk
+extern "C" void emu_features(const float* table, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype, float bound,
+                             const float* rays_o, const float* rays_d, const float* aabb, const float* z_s, uint32_t P, uint32_t T2,
+                             float* feat, float* xyz, float* inside_out) {
+  NgpLevels lv;
+  fill_levels(&lv, h_offsets, L, S, H, gridtype);
+  for (uint32_t p = 0; p < P; ++p) {
+    const uint32_t n = p / T2;
+    float x[3], x01[3];
+    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
+    const bool inside = ngp_unit(x, bound, x01);
+    ngp_encode(lv, table, x01, inside, feat + (size_t)p * NGP_FEAT);
+    for (int i = 0; i < 3; ++i) xyz[p * 3 + i] = x[i];
+    inside_out[p] = inside ? 1.0f : 0.0f;
+  }
+}
+
+extern "C" void emu_field_bwd_chunks(const float* table, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                                     const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2,
+                                     float bound, const float* rays_o, const float* rays_d, const float* aabb, const float* z_s,
+                                     const float* dsig, const float* drgb, uint32_t N, uint32_t T2, uint32_t n_chunks, const uint32_t* start,
+                                     const uint32_t* grids, float thr, const float* feat_sorted,
+                                     float* g_w0, float* g_b0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* dfeat) {
+  const uint32_t P = N * T2, T = T2 / 2;
+  std::vector<float> fc, ff;
+  std::vector<uint32_t> perm;
+  if (feat_sorted) {                               // a field cache holding the given rows behind some permutation of every ray's samples
+    fc.assign((size_t)N * T * NGP_FEAT, 0.f); ff.assign((size_t)N * T * NGP_FEAT, 0.f); perm.assign((size_t)N * T2, 0);
+    for (uint32_t p = 0; p < P; ++p) {
+      const uint32_t n = p / T2, m = p - n * T2, src = (m * 7 + 3) % T2;
+      perm[p] = src;
+      float* row = src < T ? &fc[((size_t)n * T + src) * NGP_FEAT] : &ff[((size_t)n * T + (src - T)) * NGP_FEAT];
+      for (int i = 0; i < NGP_FEAT; ++i) row[i] = feat_sorted[(size_t)p * NGP_FEAT + i];
+    }
+  }
+  float* gout[6] = {g_w0, g_b0, g_w1, g_b1, g_w2, g_b2};
+  const int glen[6] = {NGP_HID * NGP_FEAT, NGP_HID, NGP_HID * NGP_HID, NGP_HID, NGP_OUT * NGP_HID, NGP_OUT};
+  std::vector<long long> gacc[6];
+  for (int k = 0; k < 6; ++k) gacc[k].assign(glen[k], 0);
+  for (uint32_t c = 0; c < n_chunks; ++c) {
+    const uint32_t n0 = start[c], Nc = start[c + 1] - n0, P0 = n0 * T2;
+    FBArgs a{};
+    a.table = table; a.w0 = w0; a.b0 = b0; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.bound = bound;
+    a.g_w0 = gacc[0].data(); a.g_b0 = gacc[1].data(); a.g_w1 = gacc[2].data(); a.g_b1 = gacc[3].data(); a.g_w2 = gacc[4].data(); a.g_b2 = gacc[5].data();
+    a.f_w0 = g_w0; a.f_b0 = g_b0; a.f_w1 = g_w1; a.f_b1 = g_b1; a.f_w2 = g_w2; a.f_b2 = g_b2;
+    a.thr = thr;
+    fill_levels(&a.lv, h_offsets, L, S, H, gridtype);
+    a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3; a.aabb = aabb;
+    a.z_s = z_s + P0; a.dsig = dsig + P0; a.drgb = drgb + (size_t)P0 * 3; a.dfeat_out = dfeat;
+    a.P = Nc * T2; a.T2 = T2; a.dfeat_P = P; a.p_off = P0;
+    if (feat_sorted) { a.feat_c = fc.data(); a.feat_f = ff.data(); a.perm = perm.data(); }
+    hipemu::launch(grids[c], 256, FB_LDS_FLOATS * sizeof(float), [&] { k_ngp_field_bwd_mfma(a); });
+  }
+  for (int k = 0; k < 6; ++k)
+    for (int i = 0; i < glen[k]; ++i) gout[k][i] += (float)((double)gacc[k][i] * SF_FIX_INV);
+}
+
 // ---- binned table-gradient scatter (sparsefusion_amd/csrc/ngp_scatter_bin.h) against ngp_scatter (ngp_device.h), levels
 // [first_level, L); `chunks` rounds of bin + reduce over consecutive ray ranges share the entries buffer (cursor reset by the reducer)
 #include "../../sparsefusion_amd/csrc/ngp_scatter_bin.h"

@@ -179,10 +179,16 @@ def test_render_matches_reference_golden(golden, name):
 
 def test_render_backward_isolated_tight(golden):
     """C-ABI backward fed with the ORACLE's sorted samples: isolates the gradient kernels from the
-    sample-position sensitivity.  Upstream d(sigma), d(rgb) and the last layer agree to 1e-5; deeper
-    gradients differ by ReLU-mask flips of pre-activations within fp32 rounding of zero (a flip rate eps gives a
-    relative L2 difference ~sqrt(eps); measured 4e-4 .. 4e-3 on the MI355X), so the bound is 1e-2
-    in norm together with a cosine bound."""
+    sample-position sensitivity.  Upstream d(sigma), d(rgb) and the last layer agree with the fp32 torch oracle to 1e-5;
+    the deeper gradients are held to 1e-2 in norm together with a cosine bound.  That is a bound on the distance between two
+    fp32 evaluations, not on the kernels' error; the kernels' error is measured per element against float64 by
+    tests/test_gpu_ngp_bwd.py::test_golden_rays on the same 256 rays x 64 (profiles/ngp_bwd_parity_margins.log, DESIGN.md):
+    d(sigma), d(rgb), d(feat) and all six MLP gradients lie inside their derived rounding bounds (worst error / bound 0.67 for
+    d(rgb), <= 0.03 for the MLP gradients), relative L2 against float64 8e-8 .. 3.2e-7 per MLP gradient.  50 of the 32 768 points
+    have one hidden unit within the worst-case rounding margin of zero; on none of them did the kernel's ReLU mask differ from
+    the float64 sign (0 masks differed, accounting for 0 of the relative L2), on the cache and on the re-gather path.  The
+    4e-4 .. 4e-3 this docstring used to ascribe to mask flips of the kernels was never checked per element and is not their
+    rounding."""
     from sparsefusion_amd import _lib
     from sparsefusion_amd.nerf.renderer import _FieldHandle
     g = golden["teacher"]

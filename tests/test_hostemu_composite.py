@@ -83,3 +83,35 @@ def test_wave_composite_backward_matches_per_ray_loop(N, T, with_ws):
     for name, a, b in zip(("dsigma", "drgb"), got, ref):
         scale = float(b.abs().max())
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-6 * scale), (name, float((a - b).abs().max()), scale)
+
+
+@pytest.mark.parametrize("N,T,kind", [(6, 64, "random"), (5, 16, "random"), (3, 4, "random"), (24, 64, "opaque"), (9, 11, "opaque")])
+def test_wave_composite_backward_per_element_float64(N, T, kind):
+    """k_ngp_composite_bwd_wave against the float64 restatement of tests/ngp_bwd_cases.py (A), every element of d(sigma) and d(rgb) inside its
+    derived bound: the random rays of the test above, and a sigma mixture that reaches the semi-opaque (one = a few 2^-24) and the saturated
+    (one == 1e-15f) regime of after / one, whose conditions are asserted on the reference alone.  Ray 2 is a miss ray (masked)."""
+    import ngp_bwd_cases
+    lib = _lib()
+    g = torch.Generator().manual_seed(7 * N + T)
+    near = torch.rand(N, generator=g) + 0.5
+    far = near + 2.0 + torch.rand(N, generator=g)
+    z = (near[:, None] + (far - near)[:, None] * torch.rand(N, 2 * T, generator=g)).sort(1).values.contiguous()
+    z[0, 3] = z[0, 2]                                         # a zero-length interval
+    far[2] = near[2]
+    z[2] = near[2]
+    sig = (torch.rand(N, 2 * T, generator=g) * 8).contiguous() if kind == "random" else ngp_bwd_cases.opaque_sigma(z, near, far, T, N)
+    rgb = torch.rand(N, 2 * T, 3, generator=g)
+    gi = torch.randn(N, 3, generator=g)
+    gw = torch.randn(N, generator=g) if T != 16 else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    got = [torch.full((N, 2 * T), float("nan")), torch.full((N, 2 * T, 3), float("nan"))]
+    lib.emu_composite_bwd(ptr(z), ptr(sig), ptr(rgb), ptr(near), ptr(far), C.c_uint32(N), C.c_uint32(T), C.c_float(0.25), ptr(gi), ptr(gw),
+                          C.c_int(0), *[ptr(t) for t in got])
+    ref = ngp_bwd_cases.composite_bwd_ref64(z, sig, rgb, near, far, T, 0.25, gi, gw)
+    assert int(ref["mask"].sum()) == N - 1
+    if kind == "opaque":
+        semi, sat, tight = ngp_bwd_cases.opaque_conditions(ref)
+        assert semi >= 0.05 and sat >= 0.05 and tight >= 0.9, (semi, sat, tight)
+    ngp_bwd_cases.check_elements(f"emu composite {kind} {N}x{T} dsig", got[0], ref["dsig"], ref["dsig_bound"], mask=ref["mask"][:, None].expand(-1, 2 * T))
+    ngp_bwd_cases.check_elements(f"emu composite {kind} {N}x{T} drgb", got[1], ref["drgb"], ref["drgb_bound"],
+                                 mask=ref["mask"][:, None, None].expand(-1, 2 * T, 3))

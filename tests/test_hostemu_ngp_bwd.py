@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import ngp_ref
+import ngp_bwd_cases
 from hostemu import fused
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostemu")
@@ -66,6 +67,84 @@ def test_field_backward_mfma_matches_per_point_math():
     for name, a, b in zip(("g_w0", "g_b0", "g_w1", "g_b1", "g_w2", "g_b2", "dfeat"), got, ref):
         err = float((a - b).abs().max()) / max(float(b.abs().max()), 1e-20)
         assert err < 2e-5, ("cache", name, err)
+
+
+@pytest.fixture(scope="module")
+def field_problem():
+    """One small field-backward problem for the per-element checks of tests/ngp_bwd_cases.py: 13 rays x 22 sorted samples (P = 286: eight full
+    trips and a ragged one), the features ngp_encode gives them (emu_features), random upstream gradients."""
+    lib = _lib()
+    p = ngp_ref.init_params(bound=4, seed=3, table_std=0.5, sigma_bias=-1.0)
+    g = torch.Generator().manual_seed(0)
+    N, T2 = 13, 22
+    P = N * T2
+    o, d = ngp_ref.circle_rays(4, view=2)
+    o, d = o[:N].contiguous(), d[:N].contiguous()
+    z = (torch.rand(N, T2, generator=g) * 9.0 + 1.0).sort(1).values.contiguous()
+    dsig = torch.randn(P, generator=g)
+    drgb = torch.randn(P, 3, generator=g)
+    offs = p["encoder.offsets"].to(torch.int32).contiguous()
+    L = offs.numel() - 1
+    S = float(np.log2(ngp_ref.per_level_scale(4)))
+    ws = [p[f"sigma_net.net.{i}.{w}"].contiguous() for i in range(3) for w in ("weight", "bias")]
+    aabb = p["aabb_train"].contiguous()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    feat, xyz, inside = torch.zeros(P, 32), torch.zeros(P, 3), torch.zeros(P)
+    lib.emu_features(ptr(p["encoder.embeddings"]), ptr(offs), C.c_uint32(L), C.c_float(S), C.c_uint32(16), C.c_uint32(1), C.c_float(4.0), ptr(o),
+                     ptr(d), ptr(aabb), ptr(z), C.c_uint32(P), C.c_uint32(T2), ptr(feat), ptr(xyz), ptr(inside))
+    x, ins = ngp_bwd_cases.sample_points(o, d, z, aabb, 4.0)
+    assert torch.equal(x.reshape(P, 3), xyz) and torch.equal(ins.reshape(P), inside.bool())      # sample_points restates ngp_point / ngp_unit
+
+    def run(starts, grids, thr, cache, dsig=dsig, drgb=drgb):
+        out = [torch.zeros(64, 32), torch.zeros(64), torch.zeros(64, 64), torch.zeros(64), torch.zeros(4, 64), torch.zeros(4), torch.zeros(L, P, 2)]
+        st, gr = torch.tensor(starts, dtype=torch.int32), torch.tensor(grids, dtype=torch.int32)
+        lib.emu_field_bwd_chunks(ptr(p["encoder.embeddings"]), ptr(offs), C.c_uint32(L), C.c_float(S), C.c_uint32(16), C.c_uint32(1),
+                                 *[ptr(w) for w in ws], C.c_float(4.0), ptr(o), ptr(d), ptr(aabb), ptr(z), ptr(dsig), ptr(drgb), C.c_uint32(N),
+                                 C.c_uint32(T2), C.c_uint32(len(grids)), ptr(st), ptr(gr), C.c_float(thr), ptr(feat if cache else None),
+                                 *[ptr(t) for t in out])
+        return out
+
+    return dict(N=N, T=T2 // 2, P=P, W=ws, feat=feat, xyz=xyz, inside=inside.bool(), dsig=dsig, drgb=drgb, run=run)
+
+
+def _check_field(name, fp, got, geo, dsig=None, drgb=None):
+    """d(feat) and the six MLP gradients of an emulated run against the float64 reference, per element (tests/ngp_bwd_cases.py (B))."""
+    dsig, drgb = fp["dsig"] if dsig is None else dsig, fp["drgb"] if drgb is None else drgb
+    fw = ngp_bwd_cases.field_forward64(fp["feat"], fp["W"], fp["xyz"], dsig, drgb)
+    k, n_amb, n_left, P = ngp_bwd_cases.ambiguity(fw)
+    assert n_amb <= ngp_bwd_cases.AMBIGUOUS_CAP * P and n_left <= ngp_bwd_cases.LEFT_OUT_CAP * P, (n_amb, n_left, P)     # the reference alone
+    bk = ngp_bwd_cases.field_backward_check(name, fw, fp["W"], fp["inside"], got[6].permute(1, 0, 2).reshape(fp["P"], 32))
+    ref = ngp_bwd_cases.weight_grads_ref64(fw, bk, geo)
+    for key, t in zip(("w0", "b0", "w1", "b1", "w2", "b2"), got):
+        ngp_bwd_cases.check_elements(f"{name} d{key}", t, ref[key]["want"], ref[key]["bound"])
+    return ref
+
+
+@pytest.mark.parametrize("cache,starts,grids", [(False, [0, 13], [1]), (False, [0, 13], [3]), (True, [0, 13], [3]), (True, [0, 5, 13], [2, 1]),
+                                                (False, [0, 5, 13], [1, 2])])
+def test_field_backward_per_element_float64(field_problem, cache, starts, grids):
+    """k_ngp_field_bwd_mfma under the emulation against the float64 per-point reference and the derived per-element bounds: the re-gather
+    and the cache path, one workgroup (a wave runs three trips) and several, and two chunks launched as sf_ngp_render_backward launches them
+    (p_off = 110 points into the whole set's d(feat) image)."""
+    fp = field_problem
+    thr = ngp_bwd_cases.fix_thr(4.0 * sum(grids))
+    geo = ngp_bwd_cases.bwd_geometry(fp["N"], fp["T"], starts=starts, grids=grids, thr=thr)
+    ref = _check_field(f"emu cache={int(cache)} starts={starts} grids={grids}", fp, fp["run"](starts, grids, thr, cache), geo)
+    assert all(int(r["maybe_fp32"].sum()) == 0 for r in ref.values())                # every wave sum in fixed point here
+
+
+def test_field_backward_large_addends_take_the_fp32_path(field_problem):
+    """Upstream gradients scaled by 64 and thr = 8, so that some waves' sums reach thr and take sf_grad_add's fp32 atomic while others stay in
+    fixed point -- within one gradient element too (asserted on the reference's own wave sums)."""
+    fp = field_problem
+    starts, grids, thr = [0, 5, 13], [2, 1], 8.0
+    geo = ngp_bwd_cases.bwd_geometry(fp["N"], fp["T"], starts=starts, grids=grids, thr=thr)
+    dsig, drgb = fp["dsig"] * 64.0, fp["drgb"] * 64.0
+    ref = _check_field("emu large addends", fp, fp["run"](starts, grids, thr, True, dsig, drgb), geo, dsig, drgb)
+    n_waves = geo["n_waves"]
+    for key in ("w0", "w1", "w2"):
+        sure = ref[key]["sure_fp32"]
+        assert int((sure > 0).sum()) > 0 and int(((sure > 0) & (sure < n_waves)).sum()) > 0, key       # fp32 adds, and elements with both kinds
 
 
 @pytest.mark.parametrize("case", ["roomy", "overflow", "tiled"])

@@ -593,3 +593,64 @@ def test_softmax_reference_alone_stays_under_the_mismatch_cap(N):
     want, delta = nc.softmax_ref64(x, 0.125)
     fig = nc.check_bf16(f"reference alone softmax N {N}", got, want, delta)
     assert fig["worst"] <= 1
+
+
+def test_ngp_bwd_geometry_restatement_matches_the_cases():
+    """tests/ngp_bwd_cases.py restates sf_ngp_render_backward's launch geometry (ngp_bwd_plan's chunks, grid = trips < 1024 ? ceil(trips / 4) : 256,
+    wave 4 b + w takes trips 4 b + w + 4 grid i, thr_mlp = sf_fix_thr(1024 chunks)): the numbers the GPU cases of tests/test_gpu_ngp_bwd.py are
+    written for, the constants of the C++ source the restatement copies, and the wave a point lands in."""
+    import ngp_bwd_cases as nb
+    for name, c in nb.CASES.items():
+        geo = nb.bwd_geometry(c["N"], c["T"])
+        assert geo["chunks"] == c["chunks"] and geo["thr"] == c["thr"], (name, geo["chunks"], geo["thr"])
+        per_wave = torch.bincount(geo["wave"], minlength=geo["n_waves"])
+        assert int(per_wave.max()) == 32 * c["max_trips_per_wave"], name
+        assert geo["wave"].numel() == c["N"] * 2 * c["T"] and geo["n_waves"] == sum(4 * g for *_, g in c["chunks"])
+        assert float(geo["coef"].max()) == (33 * c["max_trips_per_wave"] + 2) * 2.0 ** -24
+    # wave 4 b + w of the second chunk of `two_chunks`: trips 4 b + w and 4 b + w + 1024
+    geo = nb.bwd_geometry(4096, 16)
+    assert geo["wave"][65536 + 32 * 5].item() == 1024 + 5 and geo["wave"][65536 + 32 * (1024 + 5) + 31].item() == 1024 + 5
+    # the ragged case: 26 trips on 7 workgroups, the last trip holds 14 points
+    geo = nb.bwd_geometry(37, 11)
+    assert int((geo["wave"] == 25).sum()) == 814 - 25 * 32 == 14 and int((geo["wave"] == 27).sum()) == 0
+    assert nb.bwd_plan(16384) == [0, 8192, 16384] and nb.bwd_plan(40000) == [0, 8192, 16384, 24576, 32768, 40000] and nb.bwd_plan(2048) == [0, 2048]
+    assert nb.bwd_plan(32768) == [0, 8192, 16384, 24576, 32768] and nb.bwd_plan(51712)[:2] == [0, 8192] and len(nb.bwd_plan(51712)) == 8
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "sparsefusion_amd", "csrc", "ngp_render.hip")).read()
+    for needle in ("#define NGP_BWD_CHUNKS 2u", "const uint32_t grid = trips < 1024 ? sf_div_up(trips, 4) : 256;", "sf_fix_thr(4.0 * 256.0 * n_chunks)",
+                   "(rays / k) % 256 == 0 && rays / k >= 2048", "for (uint32_t k = (N + 8191) / 8192; k > NGP_BWD_CHUNKS && k <= 64; ++k)"):
+        assert needle in src, needle
+    hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "sparsefusion_amd", "csrc", "ngp_bwd_mfma.h")).read()
+    assert "#define FB_PTS 32" in hdr and "trip = blockIdx.x * 4 + wave; trip < n_trips; trip += gridDim.x * 4" in hdr
+    assert nb.fix_thr(1024.0) == 256.0 and nb.fix_thr(12.0) == 16384.0
+
+
+def test_ngp_bwd_ambiguous_mask_inference():
+    """tests/ngp_bwd_cases.py on a point whose layer-1 unit 5 has z1 = 0 to rounding: the d(feat) row of EITHER mask is accepted and the mask is
+    inferred from it (the weight-gradient reference then follows the kernel's choice); a row with another unit flipped is refused."""
+    import ngp_bwd_cases as nb
+    g = torch.Generator().manual_seed(4)
+    P = 64
+    F = torch.randn(P, 32, generator=g)
+    W = [torch.randn(64, 32, generator=g) * 0.3, torch.randn(64, generator=g) * 0.1, torch.randn(64, 64, generator=g) * 0.2,
+         torch.randn(64, generator=g) * 0.1, torch.randn(4, 64, generator=g) * 0.2, torch.randn(4, generator=g) * 0.1]
+    W[1][5] = -float((W[0][5].double() * F[7].double()).sum())                   # z1[7, 5] = 0 up to the rounding of this bias
+    x, inside = torch.rand(P, 3, generator=g) - 0.5, torch.ones(P, dtype=torch.bool)
+    fw = nb.field_forward64(F, W, x, torch.randn(P, generator=g), torch.randn(P, 3, generator=g))
+    k, n_amb, n_left, _ = nb.ambiguity(fw)
+    assert n_amb == 1 and n_left == 0 and int(k[7]) == 1 and bool(fw["amb1"][7, 5])
+    w0, _, w1, _, w2, _ = (t.double() for t in W)
+    m1, m2 = (fw["z1"] > 0).double(), (fw["z2"] > 0).double()
+    rows = {}
+    for on in (0.0, 1.0):
+        m1[7, 5] = on
+        rows[on] = nb._backward64(fw["dout"], fw["d_dout"], m1, m2, w0, w1, w2)[4].float()
+    assert float((rows[0.0][7] - rows[1.0][7]).abs().max()) > 1e-3                # the two masks are far apart on this row
+    base = float(fw["z1"][7, 5] > 0)
+    for on in (0.0, 1.0):
+        bk = nb.field_backward_check(f"mask {on}", fw, W, inside, rows[on])
+        assert bk["inferred"] == int(on != base) and bk["ambiguous"] == 1
+        assert float(bk["dh1"][7, 5] != 0) == on or float(fw["dout"][7].abs().max()) == 0
+    m1[7, 5], m1[7, 6] = base, 1.0 - m1[7, 6]
+    wrong = nb._backward64(fw["dout"], fw["d_dout"], m1, m2, w0, w1, w2)[4].float()
+    with pytest.raises(AssertionError, match="outside their bound"):
+        nb.field_backward_check("wrong unit", fw, W, inside, wrong)
