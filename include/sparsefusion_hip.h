@@ -390,6 +390,9 @@ int sf_fusion_loss_backward(const float* img, const float* pred, const float* vi
 int sf_plan_run(const sf_op* ops, uint32_t n_ops, void* stream);
 /* Launches of k_conv_igemm_t (compile-time-geometry implicit GEMM, op flag 512) this process has made so far: dispatch tests. */
 uint64_t sf_conv_igemm_t_launches(void);
+/* Launches of the 4x4-level compile-time-geometry kernels (csrc/fused_gca4.h) so far, by family: 0 k_gca_pool4_t, 1 k_conv4_1x1_t,
+ * 2 k_gca_pool4_rc_t, 3 the (256, 16) row of k_gca_net0_t: dispatch tests. */
+uint64_t sf_gca4_launches(int family);
 /* sf_plan_run with a HIP event before every op on the launch stream; h_ms[n_ops] (host) gets per-op
  * elapsed milliseconds.  Synchronises; measurement aid for bench.py (per-kernel roofline). */
 int sf_plan_profile(const sf_op* ops, uint32_t n_ops, void* stream, float* h_ms);

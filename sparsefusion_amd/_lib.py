@@ -117,6 +117,7 @@ SIGNATURES = {
                                          c_f32p, C.c_float, u32, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "sf_plan_run": (C.c_int, [C.POINTER(SfOp), u32, C.c_void_p]),
     "sf_conv_igemm_t_launches": (u64, []),
+    "sf_gca4_launches": (u64, [C.c_int]),
     "sf_plan_profile": (C.c_int, [C.POINTER(SfOp), u32, C.c_void_p, C.c_void_p]),
     "sf_conv_packed_elems": (u64, [u32, u32, u32, u32]),
     "sf_conv_pack_weights": (C.c_int, [C.c_void_p, u32, u32, u32, u32, u32, C.c_void_p]),

@@ -12,6 +12,7 @@
 //          32 pipelined kernel (k_conv_fused_pipe: slot GroupNorm, k = 3, plain source, C % 128 == 0),
 //          16 pair: the NEXT op (an un-normalised fconv of the same tile shape) runs in the same launch (k_conv_fused_pair)
 //          64 GlobalContext pooling in the epilogue (k_conv_fused_pipe<.., POOL>), 128 keep the general kernel where k_conv4_gn would take the op
+//          256 keep the general kernel where k_conv4_1x1_t / k_gca_pool4_rc_t (fused_gca4.h) would take the op
 //   f: 0 eps  1 s1.scale  2 s2.scale
 //   norm == FNORM_ATTN (the attention core as the prologue of its output projection; k = 1, 4x4 map, C1 = 512 = 8 heads x 64):
 //      p: 0 q rows [B * 16][ldq] (instead of a source tensor)  19..21 key pointers of the <= 3 key / value segments
@@ -30,6 +31,7 @@
 #include "fused_gca.h"
 #include "fused_conv4.h"
 #include "fused_conv3s.h"
+#include "fused_gca4.h"
 
 #define SF_LDS_MAX 163840
 #ifndef SF_FCONV_WAVES
@@ -421,7 +423,7 @@ static inline int fconv_pair_setup(const sf_op& op1, const sf_op& op2, FConvPair
 
 // SF_OP_GCA operands (flags = stage)
 //   1 POOL  p: 0 h2  1 split-K slabs or null  2 conv bias or null  3 logit_part  4 part_pool  5 part_ms
-//           i: 0 M  1 C  2 HW  3 CH (pixels per chunk)  4 chunks per image  5 nparts  6 groups  7 npad
+//           i: 0 M  1 C  2 HW  3 CH (pixels per chunk)  4 chunks per image  5 nparts  6 groups  7 npad  8 bit 0: keep k_gca_pool (the 16-pixel map of a B = 1 plan runs k_gca_pool4_t otherwise)
 //   2 NET0  p: 0 part_pool  1 part_ms  2 W0 bf16 [HID][Kp]  3 b0  4 hid ;  i: 0 B  1 C  2 Kp  3 HID  4 chunks  5 bit 0: keep k_gca_net0 (the canonical (C, chunks) run k_gca_net0_t otherwise)
 //   3 GATE  p: 0 h2  1 res  2 hid  3 W2 bf16 [C][Kp2]  4 b2  5 out  6 slots or null ;  i: 0 M  1 C  2 HW  3 HID  4 Kp2  5 bit 0: keep k_gca_gate (HID = 128 | 256 | 512 run k_gca_gate_t otherwise)
 static inline int gca_setup(const sf_op& op, GcaPoolArgs& pa, GcaNetArgs& na, GcaGateArgs& ga, uint32_t& grid, char* err, size_t errn) {
@@ -458,4 +460,26 @@ static inline int gca_setup(const sf_op& op, GcaPoolArgs& pa, GcaNetArgs& na, Gc
   }
   GC_FAIL("gca: unknown stage %d", op.flags);
 #undef GC_FAIL
+}
+
+// k_gca_pool4_t (fused_gca4.h): the pooling op of a one-image 4x4 map whose (C, slabs) pair is instantiated; returns GROUPS + 1 (1 | 5) or 0 = k_gca_pool.
+#define SF_POOL4_C 1024
+static inline int gca_pool4_groups(const sf_op& op, const GcaPoolArgs& pa) {
+  if (op.flags != 1 || (op.i[8] & 1)) return 0;
+  if (pa.M != 16 || pa.HW != 16 || pa.CH != 16 || pa.chunks != 1 || pa.C != SF_POOL4_C || pa.nparts != 4 * (pa.C / 16)) return 0;
+  if (((uintptr_t)pa.h2 | (uintptr_t)pa.ws | (uintptr_t)pa.bias) & 15) return 0;
+  if (!pa.ws) return 1;
+  return (pa.groups == 4 && pa.npad == pa.C) ? 5 : 0;
+}
+
+// k_conv4_1x1_t (fused_gca4.h): the un-normalised 1x1 conv of a one-image 4x4 map on the concat of two plain sources; (CIN, COUT) = the canonical
+// UNet's res_conv.  Op flag 256 keeps the general kernel.  `pair`: the op shares its launch with the pooling op behind it (flag 16).
+#define SF_CONV4_1X1_CIN 2048
+#define SF_CONV4_1X1_COUT 1024
+static inline bool conv4_1x1_ok(const sf_op& op, const FConvArgs& a, int WM, int WN, bool pair) {
+  if ((op.flags & (1 | 2 | 4 | 8 | 32 | 64 | 256)) || (((op.flags & 16) != 0) != pair)) return false;
+  if (a.norm != FNORM_NONE || a.B != 1 || a.H != 4 || a.W != 4 || a.k != 1 || a.TR != 4 || WM != 1 || WN != 1 || a.S != 1) return false;
+  if (a.s1.mode || !a.s1.p || !a.s2.p || a.C != SF_CONV4_1X1_CIN || a.Cout != SF_CONV4_1X1_COUT || a.s1.C % 256 || a.s2.C % 256) return false;
+  if (a.ldc != a.Cout || a.co_off || a.slots_out || a.logit_part || a.dbg || !a.out) return false;
+  return (((uintptr_t)a.s1.p | (uintptr_t)a.s2.p) & 15) == 0;
 }

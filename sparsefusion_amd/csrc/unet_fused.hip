@@ -90,11 +90,24 @@ static int launch_conv3s_rc(const FConvArgs& a, uint32_t grid, hipStream_t st) {
   return SF_OK;
 }
 
+// launches of the fused_gca4.h kernels so far: [0] k_gca_pool4_t  [1] k_conv4_1x1_t  [2] k_gca_pool4_rc_t  [3] the (256, 16) row of k_gca_net0_t
+static unsigned long long g_gca4_launches[4] = {0, 0, 0, 0};
+extern "C" uint64_t sf_gca4_launches(int family) { return (family >= 0 && family < 4) ? g_gca4_launches[family] : 0; }
+
 static int run_fconv(const sf_op& op, hipStream_t st) {
   FConvArgs a;
   int WM, WN;
   uint32_t grid, lds;
   if (fconv_setup(op, a, WM, WN, grid, lds, sf_err_buf, sizeof(sf_err_buf))) return SF_ERR_INVALID;
+  if (conv4_1x1_ok(op, a, WM, WN, false)) {            // the one-image 4x4 map's plain 1x1 conv on compile-time geometry (fused_gca4.h)
+    static unsigned mask = 0;
+    constexpr uint32_t l4 = Conv41x1Geom<SF_CONV4_1X1_CIN, SF_CONV4_1X1_COUT>::LDS_BYTES;
+    if (int rc = allow_big_lds(k_conv4_1x1_t<SF_CONV4_1X1_CIN, SF_CONV4_1X1_COUT>, l4, mask)) return rc;
+    k_conv4_1x1_t<SF_CONV4_1X1_CIN, SF_CONV4_1X1_COUT><<<SF_CONV4_1X1_COUT / 16, 512, l4, st>>>(a);
+    SF_CHECK_LAUNCH("conv4_1x1_t");
+    ++g_gca4_launches[1];
+    return SF_OK;
+  }
   if (op.flags & 32) {
     const int twl = conv3s_twl(op, a, WM, WN);            // r06: the recurring geometries on their own kernel (fused_conv3s.h)
     if (twl >= 0) {
@@ -176,6 +189,20 @@ static int run_pool_rc_pair(const sf_op& op1, const sf_op& op2, hipStream_t st) 
     return SF_ERR_INVALID;
   if (op2.flags != 1 || b.norm != FNORM_NONE || b.s1.mode || WM != 1 || WN != 1 || (op1.flags & 32) || b.dbg)
     SF_FAIL(SF_ERR_INVALID, "pool || res_conv pair: a plain 16-pixel x 16-channel res_conv tile next to a pooling op required");
+  if (const int g4 = gca_pool4_groups(op2, pa); g4 && conv4_1x1_ok(op1, b, WM, WN, true) && pa.C == SF_CONV4_1X1_COUT) {      // both halves on compile-time geometry (fused_gca4.h)
+    static unsigned mask4[2] = {0, 0};
+    constexpr uint32_t l4 = Conv41x1Geom<SF_CONV4_1X1_CIN, SF_CONV4_1X1_COUT>::LDS_BYTES;
+    if (g4 == 5) {
+      if (int rc = allow_big_lds(k_gca_pool4_rc_t<SF_CONV4_1X1_CIN, SF_POOL4_C, 4>, l4, mask4[0], SF_LDS_MAX - 16384)) return rc;
+      k_gca_pool4_rc_t<SF_CONV4_1X1_CIN, SF_POOL4_C, 4><<<gb + gp, 512, l4, st>>>(pa, b, (int)gb);
+    } else {
+      if (int rc = allow_big_lds(k_gca_pool4_rc_t<SF_CONV4_1X1_CIN, SF_POOL4_C, 0>, l4, mask4[1], SF_LDS_MAX - 16384)) return rc;
+      k_gca_pool4_rc_t<SF_CONV4_1X1_CIN, SF_POOL4_C, 0><<<gb + gp, 512, l4, st>>>(pa, b, (int)gb);
+    }
+    SF_CHECK_LAUNCH("gca_pool4_rc_t");
+    ++g_gca4_launches[2];
+    return SF_OK;
+  }
   static unsigned mask = 0;
   constexpr int dyn_max = SF_LDS_MAX - 16384;                    // the pooling body keeps 9 KB of static LDS in the same kernel
   if ((int)lds > dyn_max) SF_FAIL(SF_ERR_INVALID, "pool || res_conv pair: %u bytes of LDS", lds);
@@ -247,11 +274,23 @@ static int run_gca(const sf_op& op, hipStream_t st) {
   GcaGateArgs ga;
   uint32_t grid;
   if (gca_setup(op, pa, na, ga, grid, sf_err_buf, sizeof(sf_err_buf))) return SF_ERR_INVALID;
-  if (op.flags == 1) k_gca_pool<<<grid, 256, 0, st>>>(pa);
+  if (op.flags == 1) {
+    const int g4 = gca_pool4_groups(op, pa);                   // the one-image 4x4 map on compile-time geometry (fused_gca4.h)
+    if (g4 == 5) k_gca_pool4_t<SF_POOL4_C, 4><<<grid, 256, 0, st>>>(pa);
+    else if (g4 == 1) k_gca_pool4_t<SF_POOL4_C, 0><<<grid, 256, 0, st>>>(pa);
+    else k_gca_pool<<<grid, 256, 0, st>>>(pa);
+    if (g4) ++g_gca4_launches[0];
+  }
   else if (op.flags == 2) {
     // r05: compile-time (C, chunk capacity) for the canonical UNet's blocks (i[5] & 1: keep k_gca_net0, parity tests)
 #define SF_TRYN(c_, n_) if (!(op.i[5] & 1) && na.C == c_ && na.Kp == c_ && na.chunks <= n_ && (n_ == 8 || na.chunks > n_ / 2)) { k_gca_net0_t<c_, n_><<<grid, 256, 0, st>>>(na); SF_CHECK_LAUNCH("gca_net0_t"); return SF_OK; }
     SF_TRYN(256, 64) SF_TRYN(256, 8) SF_TRYN(512, 16) SF_TRYN(512, 8) SF_TRYN(1024, 8)
+    if (!(op.i[5] & 1) && na.B == 1 && na.C == 256 && na.Kp == 256 && na.chunks > 8 && na.chunks <= 16) {      // the 16x16 down blocks of a B = 1 plan: 16 epilogue-pooled fragments
+      k_gca_net0_t<256, 16><<<grid, 256, 0, st>>>(na);
+      SF_CHECK_LAUNCH("gca_net0_t");
+      ++g_gca4_launches[3];
+      return SF_OK;
+    }
 #undef SF_TRYN
     if (na.chunks <= 8) k_gca_net0<8><<<grid, 256, 0, st>>>(na);
     else if (na.chunks <= 16) k_gca_net0<16><<<grid, 256, 0, st>>>(na);

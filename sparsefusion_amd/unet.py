@@ -59,6 +59,7 @@ SWITCHES = (
     ("lds_conv_min_blocks", 96, "use k_conv_lds when a layer has at least this many 128 x 128 output tiles"),
     ("lds_mid_min_rows", 128, "r06: convs of >= this many rows that have too few 128-row tiles for lds_conv_min_blocks run on the LDS-tiled kernels with split-K groups (Plan.conv); 0 = off"),
     ("igemm_t", 127, "the one-of-a-kind implicit GEMMs of the B = 1 eval on k_conv_igemm_t (compile-time geometry, csrc/conv_igemm_t.h; op flag 512): bit j = row j of IGEMM_T_VARIANTS; 0: k_conv_igemm"),
+    ("gca4", 15, "the 4x4 level of the B = 1 eval on compile-time geometry (csrc/fused_gca4.h): bit 0 the stand-alone GlobalContext pooling on k_gca_pool4_t (0: k_gca_pool, op field i[8] bit 0), bit 1 the stand-alone res_conv on k_conv4_1x1_t (0: k_conv_fused, op flag 256), bit 2 pooling || res_conv on k_gca_pool4_rc_t (0: k_gca_pool_rc, both), bit 3 net0 of the 16x16 down blocks on k_gca_net0_t<256, 16> (0: k_gca_net0<16>, op field i[5] bit 0)"),
     ("merged_down_conv4", True, "r06: the merged 3x3 + 1x1 conv of the last Downsample on k_conv4_gn<64, 0, false> at B = 1; False: k_conv_igemm"),
     ("rc_small_tiles", 32, "r06: bit mask of map sides (32 | 16 | 8) whose B >= 2 (conv1 || res_conv) pairs keep the B = 1 tile of k_conv3s_rc (32: B = 2 eval 1.155 -> 1.139 ms, B = 4 1.562 -> 1.520; 32 | 16: B = 4 1.580, B = 8 2.451 -> 2.550)"),
     ("gn_one", True, "r06: GroupNorm passes of B >= 32 plans (B * 8 >= 256 workgroups) in one launch (k_gn_one); False: k_gn_stats + k_gn_apply everywhere"),
@@ -396,8 +397,10 @@ class _Plan(Plan):
                     and (H.bit_length() - 1, C1, C2, Cout, (tw or H).bit_length() - 1, WM, WN) in CONV3S_RC_VARIANTS):
                 code |= (tw if tw != H else 0) << 2                # the pair runs on k_conv3s_rc (the host checks that the res_conv fits)
             ai = (code,)
+        # the B = 1 plan's plain 1x1 conv of the 4x4 map runs on k_conv4_1x1_t / k_gca_pool4_rc_t where the host has its geometry; flag 256 keeps the general kernel
+        keep4 = B == 1 and H == 4 and k == 1 and norm == FNORM_NONE and not (self.u.gca4 >> (2 if pair_first else 1)) & 1
         self.op(OP_FCONV, (1 if silu else 0) | (2 if pre_gelu else 0) | (4 if accum else 0) | (8 if out_gelu else 0) | (16 if pair_first else 0)
-                | (32 if pipe else 0) | (64 if pool is not None else 0) | (0 if self.u.conv4 else 128),
+                | (32 if pipe else 0) | (64 if pool is not None else 0) | (0 if self.u.conv4 else 128) | (256 if keep4 else 0),
                 p=(x_ptr, lp[0], lp[1], lp[2], x.slots or 0, skip.ptr if skip else 0, (skip.slots or 0) if skip else 0,
                    self.wptr(wname), 0 if S > 1 else bias, out.ptr, 0 if S > 1 else res, ws, slots_out, gam, bet, ss_ptr, 0,
                    logit[0] if logit else 0, logit[1] if logit else 0) + ap,
@@ -532,11 +535,13 @@ class _Plan(Plan):
             pp, pm = part_pool.ptr, part_ms.ptr
             if before_pool is not None:                         # the block's res_conv shares this launch (flag 16 on the fconv)
                 before_pool(True)
-            self.op(OP_GCA, 1, p=(h2.ptr, ws, bias, lpart.ptr, pp, pm), i=(rows, cout, HW, CH, chunks, nparts, groups, npad))
+            keep4 = B == 1 and HW == 16 and not (self.u.gca4 >> (2 if before_pool is not None else 0)) & 1      # i[8] bit 0: keep k_gca_pool / k_gca_pool_rc
+            self.op(OP_GCA, 1, p=(h2.ptr, ws, bias, lpart.ptr, pp, pm), i=(rows, cout, HW, CH, chunks, nparts, groups, npad, 1 if keep4 else 0))
         if want_slots:
             out.slots = self.misc.alloc(rows // 16 * (cout // 16) * 2 * 4)
         self.op(OP_GCA, 2, p=(pp, pm, self.wptr(f"{name}.gca.net.0.weight"), self.wptr(f"{name}.gca.net.0.bias"),
-                              hid.ptr), i=(B, cout, (cout + 7) // 8 * 8, hidc, chunks, 0 if self.u.gate_t else 1))
+                              hid.ptr), i=(B, cout, (cout + 7) // 8 * 8, hidc, chunks,
+                                           0 if self.u.gate_t and not (B == 1 and cout == 256 and 8 < chunks <= 16 and not self.u.gca4 & 8) else 1))
         self.op(OP_GCA, 3, p=(h2.ptr, res.ptr, hid.ptr, self.wptr(f"{name}.gca.net.2.weight"), self.wptr(f"{name}.gca.net.2.bias"),
                               out.ptr, out.slots or 0), i=(rows, cout, HW, hidc, (hidc + 7) // 8 * 8, 0 if self.u.gate_t else 1))
 
