@@ -304,6 +304,20 @@ int sf_ngp_render_occ_eval(const sf_ngp_field* f, const float* rays_o, const flo
                            const float* noises, float T_thresh, uint32_t N,
                            float* weights_sum, float* depth, float* image, void* stream);
 
+/* The same evaluation render, Lambertian-shaded (run_cuda with shading='lambertian', eval mode): per occupied sample the
+ * finite-difference normal of sf_ngp_point_attrs with `epsilon` (the same bits) and the colour
+ * albedo * (ambient_ratio + (1 - ambient_ratio) * max(n . -light_d, 0)), composited as sf_ngp_render_occ_eval composites the
+ * albedo: at ambient_ratio = 1 image / depth / weights_sum are that entry's, bit for bit.  One launch, eight lanes per ray
+ * (csrc/ngp_occ_shade.h).  light_d: 3 floats ON THE DEVICE.  SF_ERR_INVALID before any launch: whatever sf_ngp_render_occ_eval
+ * rejects, NULL light_d, epsilon not finite or <= 0, ambient_ratio not finite, N >= 2^29.  N == 0: SF_OK, no launch. */
+int sf_ngp_render_occ_eval_shaded(const sf_ngp_field* f, const float* rays_o, const float* rays_d,
+        const float* nears, const float* fars, const uint8_t* grid, float dt_gamma, uint32_t max_steps,
+        uint32_t C, uint32_t H, const float* noises, float T_thresh, uint32_t N,
+        const float* light_d /* 3 floats ON THE DEVICE */, float ambient_ratio, float epsilon,
+        float* weights_sum, float* depth, float* image,          /* as sf_ngp_render_occ_eval: no background, depth un-normalised */
+        float* normal_image /* [N,3] sum w n, or NULL */, uint32_t* n_samples /* [N] samples composited, or NULL */,
+        void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* UNet op executor (external/imagen_pytorch.py:1470-1671) -- the host side  */
 /* builds a static launch plan once (sparsefusion_amd/unet.py) and the       */

@@ -115,6 +115,9 @@ SIGNATURES = {
     "sf_ngp_render_shaded_workspace_bytes": (u64, [u32, u32]),
     "sf_ngp_render_occ_eval": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_float, u32, u32, u32,
                                          c_f32p, C.c_float, u32, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "sf_ngp_render_occ_eval_shaded": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_float, u32, u32,
+                                                u32, c_f32p, C.c_float, u32, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p,
+                                                c_f32p, C.c_void_p, C.c_void_p]),
     "sf_plan_run": (C.c_int, [C.POINTER(SfOp), u32, C.c_void_p]),
     "sf_conv_igemm_t_launches": (u64, []),
     "sf_gca4_launches": (u64, [C.c_int]),

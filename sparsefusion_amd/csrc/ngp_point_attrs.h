@@ -21,6 +21,25 @@ struct NgpPointAttrs { float sigma; float albedo[3]; float grad[3]; float normal
 // torch.clamp(v, -b, b): NaN propagates (fminf / fmaxf alone would return the bound)
 SF_HD float ngp_clamp_sym(float v, float b) { return (v != v) ? v : fminf(fmaxf(v, -b), b); }
 
+// The finite-difference arithmetic, shared by ngp_point_attrs below and the eight-lanes-per-ray shaded render (ngp_occ_shade.h),
+// whose normals are therefore the same bits: one component of the gradient from the sigmas at x + eps e_a and x - eps e_a ...
+SF_HD float ngp_fd_grad(float sp, float sn, float eps) { return SF_DIV(SF_MUL(0.5f, SF_SUB(sp, sn)), eps); }
+// ... and safe_normalize of the gradient, NaN components -> 0
+SF_HD void ngp_fd_normal(const float g[3], float n[3]) {
+  const float len = sqrtf(fmaxf(SF_ADD(SF_ADD(SF_MUL(g[0], g[0]), SF_MUL(g[1], g[1])), SF_MUL(g[2], g[2])), 1e-20f));
+  const float nx = SF_DIV(g[0], len), ny = SF_DIV(g[1], len), nz = SF_DIV(g[2], len);
+  n[0] = (nx != nx) ? 0.0f : nx;
+  n[1] = (ny != ny) ? 0.0f : ny;
+  n[2] = (nz != nz) ? 0.0f : nz;
+}
+
+// lambertian = ratio + (1 - ratio) * clamp(n @ (-l), min=0); the dot product left to right, nothing contracted
+SF_HD float ngp_lambertian(const float n[3], const float l[3], float ratio) {
+  const float dot = SF_ADD(SF_ADD(SF_MUL(n[0], -l[0]), SF_MUL(n[1], -l[1])), SF_MUL(n[2], -l[2]));
+  const float lit = (dot != dot) ? dot : fmaxf(dot, 0.0f);       // torch.clamp keeps NaN
+  return SF_ADD(ratio, SF_MUL(SF_SUB(1.0f, ratio), lit));
+}
+
 // n_eval = 7: everything; n_eval = 1: sigma and albedo only (grad and normal are left untouched); first_eval = 1: the centre is
 // skipped (sigma and albedo are left untouched: the caller already holds that point's values -- k_ngp_shade, ngp_shade.h)
 SF_HD void ngp_point_attrs(const NgpLevels& lv, const float* __restrict__ table, const float* __restrict__ W, float bound,
@@ -48,7 +67,7 @@ SF_HD void ngp_point_attrs(const NgpLevels& lv, const float* __restrict__ table,
     } else if (e & 1) {
       sp = s;
     } else {
-      const float g = SF_DIV(SF_MUL(0.5f, SF_SUB(sp, s)), eps);
+      const float g = ngp_fd_grad(sp, s, eps);
       if (axis == 0) gx = g;
       else if (axis == 1) gy = g;
       else gz = g;
@@ -58,9 +77,5 @@ SF_HD void ngp_point_attrs(const NgpLevels& lv, const float* __restrict__ table,
   a.grad[0] = gx;
   a.grad[1] = gy;
   a.grad[2] = gz;
-  const float len = sqrtf(fmaxf(SF_ADD(SF_ADD(SF_MUL(gx, gx), SF_MUL(gy, gy)), SF_MUL(gz, gz)), 1e-20f));
-  const float nx = SF_DIV(gx, len), ny = SF_DIV(gy, len), nz = SF_DIV(gz, len);
-  a.normal[0] = (nx != nx) ? 0.0f : nx;
-  a.normal[1] = (ny != ny) ? 0.0f : ny;
-  a.normal[2] = (nz != nz) ? 0.0f : nz;
+  ngp_fd_normal(a.grad, a.normal);
 }

@@ -28,13 +28,7 @@ struct ShadeArgs {
   float* normal_s; float* rgb_shaded_s; float* xyz_s;            // [N][2T][3] each; xyz_s or null
 };
 
-// lambertian = ratio + (1 - ratio) * clamp(n @ (-l), min=0); the dot product left to right, nothing contracted
-SF_DEV float ngp_lambertian(const float n[3], const float l[3], float ratio) {
-  const float dot = SF_ADD(SF_ADD(SF_MUL(n[0], -l[0]), SF_MUL(n[1], -l[1])), SF_MUL(n[2], -l[2]));
-  const float lit = (dot != dot) ? dot : fmaxf(dot, 0.0f);       // torch.clamp keeps NaN
-  return SF_ADD(ratio, SF_MUL(SF_SUB(1.0f, ratio), lit));
-}
-
+// ngp_lambertian (ambient + diffuse factor of one sample) lives in ngp_point_attrs.h, next to the normal it shades
 SF_KERNEL(256) void k_ngp_shade(ShadeArgs a) {
   SF_SHARED __attribute__((aligned(16))) float W[NGP_WTOTAL];
   load_weights_lds(W, a.f);

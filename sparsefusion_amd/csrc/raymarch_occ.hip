@@ -19,86 +19,13 @@
 
 #include "sf_common.h"
 #include "ngp_field_lds.h"
+#include "occ_marcher.h"                 // Marcher, clampf, signf1, mip_from_*, SF_SQRT3
+#include "ngp_occ_shade.h"               // k_render_occ_eval_shaded
 #include <float.h>
 
-#define SF_SQRT3 1.7320508075688772f
 #define SF_RPI 0.3183098861837907f
 #define MARCH_BLOCK 256
 #define SCAN_RAYS 1024                       // rays per scan workgroup (256 lanes x 4)
-
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
-__device__ __forceinline__ float signf1(float x) { return copysignf(1.0f, x); }
-
-__device__ __forceinline__ uint32_t occ_expand_bits(uint32_t v) {
-  v = (v * 0x00010001u) & 0xFF0000FFu;
-  v = (v * 0x00000101u) & 0x0F00F00Fu;
-  v = (v * 0x00000011u) & 0xC30C30C3u;
-  v = (v * 0x00000005u) & 0x49249249u;
-  return v;
-}
-
-__device__ __forceinline__ int mip_from_pos(float x, float y, float z, float max_cascade) {
-  const float mx = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
-  int e;
-  (void)frexpf(mx, &e);
-  return (int)fminf(max_cascade - 1.0f, fmaxf(0.0f, (float)e));
-}
-__device__ __forceinline__ int mip_from_dt(float dt, float H, float max_cascade) {
-  const float mx = (float)((double)(dt * H) * 0.5);
-  int e;
-  (void)frexpf(mx, &e);
-  return (int)fminf(max_cascade - 1.0f, fmaxf(0.0f, (float)e));
-}
-
-// State of one marching ray; `probe` classifies the sample at the current t, `skip` jumps an empty cell.
-struct Marcher {
-  float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz, rH, H3, bound, dt_gamma, dt_min, dt_max;
-  uint32_t C, H;
-  const uint8_t* grid;
-
-  __device__ __forceinline__ void init(const float* o, const float* d, const uint8_t* g, float bnd, float gamma,
-                                       uint32_t max_steps, uint32_t c, uint32_t h) {
-    ox = o[0]; oy = o[1]; oz = o[2]; dx = d[0]; dy = d[1]; dz = d[2];
-    rdx = __fdiv_rn(1.0f, dx); rdy = __fdiv_rn(1.0f, dy); rdz = __fdiv_rn(1.0f, dz);
-    rH = __fdiv_rn(1.0f, (float)h);
-    H3 = (float)(h * h * h);
-    bound = bnd; dt_gamma = gamma; C = c; H = h; grid = g;
-    dt_min = __fdiv_rn(2.0f * SF_SQRT3, (float)max_steps);
-    dt_max = __fdiv_rn(2.0f * SF_SQRT3 * (float)(1 << (c - 1)), (float)h);
-  }
-  __device__ __forceinline__ float step_size(float t) const { return clampf(t * dt_gamma, dt_min, dt_max); }
-
-  // returns occupancy of the cell holding the sample at t; fills the clamped position, dt and the cell geometry
-  __device__ __forceinline__ bool probe(float t, float& x, float& y, float& z, float& dt, int& nx, int& ny, int& nz,
-                                        float& mip_bound) const {
-    x = clampf(fmaf(t, dx, ox), -bound, bound);
-    y = clampf(fmaf(t, dy, oy), -bound, bound);
-    z = clampf(fmaf(t, dz, oz), -bound, bound);
-    dt = step_size(t);
-    const int l0 = mip_from_pos(x, y, z, (float)C), l1 = mip_from_dt(dt, (float)H, (float)C);
-    const int level = l0 > l1 ? l0 : l1;
-    mip_bound = fminf(scalbnf(1.0f, level), bound);
-    const float mip_rbound = __fdiv_rn(1.0f, mip_bound);
-    const float hi = (float)(H - 1);
-    // `0.5 * (...) * H` is evaluated in double (0.5 is a double literal), then narrowed for clamp()
-    nx = (int)clampf((float)(0.5 * (double)fmaf(x, mip_rbound, 1.0f) * (double)H), 0.0f, hi);
-    ny = (int)clampf((float)(0.5 * (double)fmaf(y, mip_rbound, 1.0f) * (double)H), 0.0f, hi);
-    nz = (int)clampf((float)(0.5 * (double)fmaf(z, mip_rbound, 1.0f) * (double)H), 0.0f, hi);
-    // level * H3 is a float product converted to uint32 after the integer Morton code is added in float
-    const uint32_t morton = occ_expand_bits((uint32_t)nx) | (occ_expand_bits((uint32_t)ny) << 1) | (occ_expand_bits((uint32_t)nz) << 2);
-    const uint32_t index = (uint32_t)((float)level * H3 + (float)morton);
-    return (grid[index >> 3] >> (index & 7u)) & 1u;
-  }
-  // advance t past the empty cell (nx, ny, nz)
-  __device__ __forceinline__ float skip(float t, float x, float y, float z, int nx, int ny, int nz, float mip_bound) const {
-    const float tx = (fmaf(((float)nx + 0.5f + 0.5f * signf1(dx)) * rH * 2.0f - 1.0f, mip_bound, -x)) * rdx;
-    const float ty = (fmaf(((float)ny + 0.5f + 0.5f * signf1(dy)) * rH * 2.0f - 1.0f, mip_bound, -y)) * rdy;
-    const float tz = (fmaf(((float)nz + 0.5f + 0.5f * signf1(dz)) * rH * 2.0f - 1.0f, mip_bound, -z)) * rdz;
-    const float tt = t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
-    do { t += step_size(t); } while (t < tt);
-    return t;
-  }
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // sph_from_ray
@@ -567,5 +494,34 @@ extern "C" int sf_ngp_render_occ_eval(const sf_ngp_field* f, const float* rays_o
                                                                          dt_gamma, max_steps, C, H, noises, T_thresh, N,
                                                                          weights_sum, depth, image);
   SF_CHECK_LAUNCH("render_occ_eval");
+  return SF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Lambertian-shaded evaluation render: k_render_occ_eval_shaded (ngp_occ_shade.h), eight lanes per ray
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int sf_ngp_render_occ_eval_shaded(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* nears,
+                                             const float* fars, const uint8_t* grid, float dt_gamma, uint32_t max_steps, uint32_t C,
+                                             uint32_t H, const float* noises, float T_thresh, uint32_t N, const float* light_d,
+                                             float ambient_ratio, float epsilon, float* weights_sum, float* depth, float* image,
+                                             float* normal_image, uint32_t* n_samples, void* stream) {
+  if (!light_d) SF_FAIL(SF_ERR_INVALID, "render_occ_eval_shaded: light_d is null");
+  if (!isfinite(epsilon) || !(epsilon > 0.0f)) SF_FAIL(SF_ERR_INVALID, "render_occ_eval_shaded: epsilon must be finite and > 0");
+  if (!isfinite(ambient_ratio)) SF_FAIL(SF_ERR_INVALID, "render_occ_eval_shaded: ambient_ratio must be finite");
+  if (N >= (1u << 29)) SF_FAIL(SF_ERR_INVALID, "render_occ_eval_shaded: N must be below 2^29 (the kernel indexes 8 N lanes)");
+  if (N == 0) return SF_OK;
+  if (!f || !rays_o || !rays_d || !nears || !fars || !grid || !weights_sum || !depth || !image)
+    SF_FAIL(SF_ERR_INVALID, "render_occ_eval_shaded: null tensor");
+  if (C < 1 || C > 16 || H < 1 || H > 1024 || max_steps < 1)
+    SF_FAIL(SF_ERR_INVALID, "render_occ_eval_shaded: cascade / grid size / steps out of range");
+  OccShadeArgs a{};
+  if (int rc = sf_ngp_make_levels(f, &a.lv, (hipStream_t)stream)) return rc;
+  a.f = sf_ngp_field_ptrs(f);
+  a.rays_o = rays_o; a.rays_d = rays_d; a.nears = nears; a.fars = fars; a.grid = grid; a.noises = noises; a.light_d = light_d;
+  a.dt_gamma = dt_gamma; a.T_thresh = T_thresh; a.ratio = ambient_ratio; a.eps = epsilon;
+  a.max_steps = max_steps; a.C = C; a.H = H; a.N = N;
+  a.weights_sum = weights_sum; a.depth = depth; a.image = image; a.normal_image = normal_image; a.n_samples = n_samples;
+  k_render_occ_eval_shaded<<<sf_div_up(N, 32u), 256, 0, (hipStream_t)stream>>>(a);
+  SF_CHECK_LAUNCH("render_occ_eval_shaded");
   return SF_OK;
 }

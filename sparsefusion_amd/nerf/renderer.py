@@ -411,7 +411,8 @@ class NeRFRenderer(nn.Module):
             evaluates the fused field at the occupied samples until it is opaque / leaves the box.  The reference's rounds of
             march_rays -> network -> composite_rays over a shrinking alive list need a host read per round; with
             perturb=False (the reference's evaluation setting, renderer_df.py:653-717 via render_batched) the samples of a
-            ray and the arithmetic on them do not depend on that batching, so the result is the same.  DEVIATION with
+            ray and the arithmetic on them do not depend on that batching, so the result is the same (up to the ulp or two by which
+            a round's restart point, near + the composited gaps, misses the marcher's t on a few rays).  DEVIATION with
             perturb=True: the reference restarts every round from rays_t = near + sum of the deltas it composited, which
             lags the jittered t by step * noise (raymarching.cu:736-748, renderer_df.py:548), so later rounds re-jitter
             from a slightly earlier t; this kernel keeps marching from the true t.  The sample sets differ by less than
@@ -420,15 +421,51 @@ class NeRFRenderer(nn.Module):
           * training keeps the three stages (the samples must exist as tensors for autograd): slot assignment by a block
             scan (raymarching.march_rays_train), field query through the differentiable grid-encode op, compositing with
             its own backward kernel.
-        `noise` = per-ray jitter tensor [N] in place of torch.rand."""
+        `noise` = per-ray jitter tensor [N] in place of torch.rand.
+
+        shading='lambertian' (renderer_df.py:503, 550 pass light_d / ambient_ratio / shading to the network in both modes) is
+        rendered in EVALUATION mode only: near / far as for 'albedo', then one launch of sf_ngp_render_occ_eval_shaded
+        (csrc/ngp_occ_shade.h: eight lanes per ray, the seven field evaluations of a sample side by side), no gradient, detached
+        parameters.  Per occupied sample the finite-difference normal (epsilon 1e-2, the reference's) and albedo * (ambient_ratio
+        + (1 - ambient_ratio) * max(n . -light_d, 0)).  `light_d`: any 3-vector; None draws safe_normalize(rays_o[0] + randn(3))
+        (:486-489) on the device.  The result then also holds 'normal' [..., 3] = sum w n -- an extension, as in `run`; no
+        'loss_orient' (the reference's evaluation branch returns none).  In training mode a non-albedo shading raises: the
+        three-stage training path has no shaded form.  'textureless' and 'normal' raise in both modes (the reference's random
+        smooth normal).  shading='albedo' consumes no random draw for the light."""
         from .. import raymarching
-        if shading != 'albedo':
-            raise NotImplementedError("only shading='albedo' is on the distillation path (distillation.py:209,282)")
+        if shading not in ('albedo', 'lambertian'):
+            raise NotImplementedError(f"shading={shading!r}: only 'albedo' and 'lambertian' are rendered ('textureless' and 'normal' use "
+                                      "the reference's random smooth normal, common_forward_smooth, which is not reproduced)")
+        shaded = shading == 'lambertian'
+        if shaded and self.training:
+            raise NotImplementedError("shading='lambertian' through the occupancy grid is an evaluation render (call .eval() first): "
+                                      "the three-stage training path (march_rays_train / field / composite_rays_train) has no shaded "
+                                      "form; only shading='albedo' is on the distillation path (distillation.py:209,282)")
+        if shaded and light_d is not None:
+            light_d = torch.as_tensor(light_d)
+            if light_d.numel() != 3:
+                raise ValueError("light_d must be a 3-vector")
         lead = rays_o.shape[:-1]
         o = rays_o.contiguous().view(-1, 3).float()
         d = rays_d.contiguous().view(-1, 3).float()
+        if shaded:
+            _lib.require_cuda(o, d)
         box = self.aabb_train if self.training else self.aabb_infer
         nears, fars = raymarching.near_far_from_aabb(o, d, box)
+        if shaded:
+            if light_d is not None:
+                light = light_d.detach().reshape(3).to(device=o.device, dtype=torch.float32)
+            else:
+                light = safe_normalize(o[0] + torch.randn(3, device=o.device, dtype=torch.float))      # renderer_df.py:486-489
+            opacity, z, rgb, nimg = self._occ_eval_shaded(o, d, nears, fars, dt_gamma, perturb, max_steps, T_thresh, noise,
+                                                          light.contiguous(), float(ambient_ratio))
+            background = 1 if bg_color is None else bg_color
+            rgb = rgb + (1 - opacity).unsqueeze(-1) * background
+            return {'image': rgb.view(*lead, 3),
+                    'depth': (torch.clamp(z - nears, min=0) / (fars - nears)).view(*lead),
+                    'weights_sum': opacity.reshape(*lead),
+                    'mask': (nears < fars).reshape(*lead),
+                    'normal': nimg.view(*lead, 3)}
         stage = self._occ_train if self.training else self._occ_eval
         opacity, z, rgb = stage(o, d, nears, fars, dt_gamma, perturb, force_all_rays, max_steps, T_thresh, noise, ambient_ratio)
         background = 1 if bg_color is None else bg_color
@@ -468,6 +505,28 @@ class NeRFRenderer(nn.Module):
         _lib.check(rc, "ngp_render_occ_eval")
         return opacity, z, rgb
 
+    @torch.no_grad()
+    def _occ_eval_shaded(self, o, d, nears, fars, dt_gamma, perturb, max_steps, T_thresh, noise, light, ratio, epsilon=1e-2):
+        """One sf_ngp_render_occ_eval_shaded call (csrc/ngp_occ_shade.h); `light` [3] stays on the device."""
+        N, dev = o.shape[0], o.device
+        if perturb and noise is None:
+            noise = torch.rand(N, dtype=torch.float32, device=dev)
+        jitter = noise.float().contiguous() if (perturb and noise is not None) else None
+        f32 = dict(dtype=torch.float32, device=dev)
+        opacity, z = torch.empty(N, **f32), torch.empty(N, **f32)
+        rgb, nimg = torch.empty(N, 3, **f32), torch.empty(N, 3, **f32)
+        params = [p.detach().contiguous() for p in self._field_params()]
+        bits = self.density_bitfield.contiguous()
+        _lib.require_cuda(o, d, nears, fars, bits, jitter, light, *params)
+        f = self._field_handle().struct(params)
+        rc = _lib.lib().sf_ngp_render_occ_eval_shaded(C.byref(f), _lib.ptr(o), _lib.ptr(d), _lib.ptr(nears), _lib.ptr(fars),
+                                                      _lib.ptr(bits), float(dt_gamma), int(max_steps), int(self.cascade),
+                                                      int(self.grid_size), _lib.ptr(jitter), float(T_thresh), N, _lib.ptr(light),
+                                                      float(ratio), float(epsilon), _lib.ptr(opacity), _lib.ptr(z), _lib.ptr(rgb),
+                                                      _lib.ptr(nimg), None, _lib.stream_ptr())
+        _lib.check(rc, "ngp_render_occ_eval_shaded")
+        return opacity, z, rgb, nimg
+
     def _run(self, rays_o, rays_d, **kwargs):
         """renderer_df.py:647-650: the occupancy-grid marcher when cuda_ray, the fused coarse+fine sampler otherwise."""
         return (self.run_cuda if self.cuda_ray else self.run)(rays_o, rays_d, **kwargs)
@@ -485,7 +544,7 @@ class NeRFRenderer(nn.Module):
                 depth[b:b + 1, head:tail] = r['depth']
                 weights_sum[b:b + 1, head:tail] = r['weights_sum']
                 image[b:b + 1, head:tail] = r['image']
-                if 'normal' in r:                               # shaded chunks (run, shading='lambertian'): the normal map
+                if 'normal' in r:                               # shaded chunks (run / run_cuda, shading='lambertian'): the normal map
                     if normal is None:
                         normal = torch.empty((B, N, 3), device=dev)
                     normal[b:b + 1, head:tail] = r['normal']
