@@ -82,6 +82,19 @@ int sf_morton3D_invert(const int32_t* indices, uint32_t N, int32_t* coords, void
 int sf_packbits(const float* grid, uint32_t N, float density_thresh,
                 uint8_t* bitfield, void* stream);
 
+/* Camera-coverage culling of the cascaded density grid (NeRFRenderer.mark_untrained_grid, external/nerf/renderer.py:379-442):
+ * every cell of every cascade that none of the B cameras covers gets density_grid = -1 (whatever it held); covered cells are
+ * not written.  One launch, one lane per Morton index (csrc/occ_mark.h states the float32 test operation by operation).
+ * poses [B,4,4] camera-to-world, row-major; intrinsics [B,4] = fx fy cx cy per camera; density_grid [C, H^3] in Morton order.
+ * count, if not NULL, receives the number of covering cameras per cell ([C, H^3]); with count == NULL a wave stops at the
+ * first camera after which all its cells are covered.  n_marked (one word) is zeroed by the entry and receives the number of
+ * cells set to -1.  SF_ERR_INVALID before any device call: NULL density_grid / n_marked, NULL poses / intrinsics with B > 0,
+ * C outside 1..16, H not a power of two in 2..1024, bound not finite or <= 0.  B == 0 is legal and marks every cell. */
+int sf_occ_mark_untrained(const float* poses /* [B,4,4] c2w, row-major */, const float* intrinsics /* [B,4] fx fy cx cy */,
+                          uint32_t B, float bound, uint32_t C /* cascades */, uint32_t H /* power of two */,
+                          float* density_grid /* [C,H^3] in place */, int32_t* count /* [C,H^3] or NULL */,
+                          uint32_t* n_marked /* 1 word, zeroed by the entry */, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* `_raymarching` occupancy-grid entry points (cuda_ray=True path):          */
 /* raymarching/src/bindings.cpp:8,12-18, raymarching.h:8,12-18.              */

@@ -5,10 +5,12 @@
 //   near_far_from_aabb   raymarching/src/raymarching.cu:91-156
 //   morton3D / invert    raymarching/src/raymarching.cu:56-82, :214-254
 //   packbits             raymarching/src/raymarching.cu:267-289
+// and holds the entry of the camera-coverage culling of the density grid (occ_mark.h; NeRFRenderer.mark_untrained_grid).
 // fp32 compare order and the 1/d reciprocal are kept exactly (bit-exact near/far).
 // All kernels are one element per lane, grid-stride, coalesced; HBM-bound.
 
 #include "sf_common.h"
+#include "occ_mark.h"                    // sf_compact_bits, k_occ_mark_untrained
 #include <float.h>
 
 __global__ __launch_bounds__(256) void k_near_far_from_aabb(
@@ -46,14 +48,6 @@ __device__ __forceinline__ uint32_t sf_expand_bits(uint32_t v) {
   v = (v * 0x00000011u) & 0xC30C30C3u;
   v = (v * 0x00000005u) & 0x49249249u;
   return v;
-}
-__device__ __forceinline__ uint32_t sf_compact_bits(uint32_t x) {
-  x = x & 0x49249249u;
-  x = (x | (x >> 2)) & 0xc30c30c3u;
-  x = (x | (x >> 4)) & 0x0f00f00fu;
-  x = (x | (x >> 8)) & 0xff0000ffu;
-  x = (x | (x >> 16)) & 0x0000ffffu;
-  return x;
 }
 
 __global__ __launch_bounds__(256) void k_morton3D(const int32_t* __restrict__ coords, uint32_t N,
@@ -126,5 +120,27 @@ extern "C" int sf_packbits(const float* grid, uint32_t N, float density_thresh, 
   if (!grid || !bitfield) SF_FAIL(SF_ERR_INVALID, "packbits: null tensor");
   k_packbits<<<sf_grid_cap(sf_div_up(N, 256)), 256, 0, (hipStream_t)stream>>>(grid, N, density_thresh, bitfield);
   SF_CHECK_LAUNCH("packbits");
+  return SF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mark_untrained_grid: k_occ_mark_untrained (occ_mark.h), one lane per Morton index, all cascades and cameras in one launch
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int sf_occ_mark_untrained(const float* poses, const float* intrinsics, uint32_t B, float bound, uint32_t C, uint32_t H,
+                                     float* density_grid, int32_t* count, uint32_t* n_marked, void* stream) {
+  if (!density_grid || !n_marked || (B && (!poses || !intrinsics))) SF_FAIL(SF_ERR_INVALID, "occ_mark_untrained: null tensor");
+  if (C < 1 || C > 16) SF_FAIL(SF_ERR_INVALID, "occ_mark_untrained: cascades out of range (1..16)");
+  if (H < 2 || H > 1024 || (H & (H - 1))) SF_FAIL(SF_ERR_INVALID, "occ_mark_untrained: grid size must be a power of two in 2..1024");
+  if (!isfinite(bound) || !(bound > 0.0f)) SF_FAIL(SF_ERR_INVALID, "occ_mark_untrained: bound must be finite and > 0");
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(n_marked, 0, sizeof(uint32_t), st) != hipSuccess) {
+    (void)hipGetLastError();
+    SF_FAIL(SF_ERR_LAUNCH, "occ_mark_untrained: clearing n_marked failed");
+  }
+  OccMarkArgs a{};
+  a.poses = poses; a.intrinsics = intrinsics; a.B = B; a.C = C; a.H = H; a.bound = bound;
+  a.grid = density_grid; a.count = count; a.n_marked = n_marked;
+  k_occ_mark_untrained<<<occ_mark_grid(H), OCC_MARK_BLOCK, 0, st>>>(a);
+  SF_CHECK_LAUNCH("occ_mark_untrained");
   return SF_OK;
 }

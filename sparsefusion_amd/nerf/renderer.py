@@ -262,6 +262,25 @@ class NeRFRenderer(nn.Module):
         return world, faces, colors, normals
 
     @torch.no_grad()
+    def mark_untrained_grid(self, poses, intrinsic, S=64, return_count=False):
+        """Camera-coverage culling of the density grid (external/nerf/renderer.py:379-442; the reference's trainer calls it once
+        before the first epoch): every cell of every cascade that none of the cameras sees is set to -1, whatever it held.
+        update_extra_state never revives such a cell and packbits never sets its bit, so the marcher never samples it.  One launch
+        over the grid in storage order (raymarching.mark_untrained, csrc/occ_mark.h) instead of the reference's blocked loop.
+
+        `poses` [B, 4, 4] camera-to-world: a tensor on any device or an np.ndarray.  `intrinsic`: (fx, fy, cx, cy) as a list, tuple,
+        array or tensor -- the reference's form -- or [B, 4], one row per camera (an extension).  A cell centre p is seen by a camera
+        when, with cam = (p - t) @ R, cam_z > 0, |cam_x| < cx / fx * cam_z + cell and |cam_y| < cy / fy * cam_z + cell, cell the
+        cell's edge in its cascade.  Returns None without cuda_ray, as the reference; otherwise the number of cells marked (the
+        reference prints it; nothing is printed here), or with return_count (an extension) the pair (n_marked, count), count
+        [cascade, H^3] int32 = the number of cameras that see each cell.  `S` is accepted for call compatibility and ignored:
+        there are no chunks.  The bitfield is not touched: the next update_extra_state packs it, as in the reference."""
+        if not self.cuda_ray:
+            return None
+        from .. import raymarching
+        return raymarching.mark_untrained(poses, intrinsic, self.bound, self.density_grid, return_count=return_count)
+
+    @torch.no_grad()
     def update_extra_state(self, decay=0.95, S=128, noise=None):
         """EMA update of the cascaded density grid, its bitfield and the mean sample count (renderer_df.py:586-638).
 
@@ -286,7 +305,9 @@ class NeRFRenderer(nn.Module):
             tmp_grid[cas] = self.density(pts)['sigma'].reshape(-1)
         valid = self.density_grid >= 0                                    # cells never marked invalid (< 0) take the EMA / max rule
         self.density_grid[valid] = torch.maximum(self.density_grid[valid] * decay, tmp_grid[valid])
-        self.mean_density = torch.mean(self.density_grid[valid]).item()
+        # renderer.py:524: cells marked -1 (mark_untrained_grid) count as zero density; flattened, so that without a marked cell the
+        # reduction sees the tensor the mean over the valid cells saw
+        self.mean_density = torch.mean(self.density_grid.clamp(min=0).reshape(-1)).item()
         self.iter_density += 1
         self.density_bitfield = raymarching.packbits(self.density_grid, min(self.mean_density, self.density_thresh),
                                                      self.density_bitfield)

@@ -45,6 +45,34 @@ def packbits(grid, thresh, bitfield=None):
     return bitfield
 
 
+@torch.no_grad()
+def mark_untrained(poses, intrinsics, bound, density_grid, return_count=False):
+    """Camera-coverage culling of a cascaded density grid [C, H^3] (Morton order), in place: every cell that none of the B
+    cameras covers becomes -1 (sf_occ_mark_untrained, csrc/occ_mark.h).  `poses` [B, 4, 4] camera-to-world and `intrinsics`
+    [4] or [B, 4] = (fx, fy, cx, cy): tensors on any device, strided or not, or numpy arrays.  Returns the number of cells
+    marked, or (that, count [C, H^3] int32 = covering cameras per cell) with return_count.  Not in the reference's
+    raymarching module: its NeRFRenderer.mark_untrained_grid is a Python loop (external/nerf/renderer.py:379-442)."""
+    dev = density_grid.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    P = torch.as_tensor(poses).to(**f32).reshape(-1, 4, 4).contiguous()
+    B = P.shape[0]
+    K = torch.as_tensor(intrinsics).to(**f32)
+    if K.numel() == 4:
+        K = K.reshape(1, 4).expand(B, 4)
+    if K.shape != (B, 4):
+        raise ValueError("intrinsics must be 4 numbers (fx, fy, cx, cy) or [B, 4]")
+    K = K.contiguous()
+    Cc, H3 = density_grid.shape
+    H = round(H3 ** (1.0 / 3.0))
+    if H ** 3 != H3:
+        raise ValueError("density_grid must be [cascades, H^3]")
+    count = torch.empty(Cc, H3, dtype=torch.int32, device=dev) if return_count else None
+    n_marked = torch.empty(1, dtype=torch.int32, device=dev)
+    backend.occ_mark_untrained(P, K, B, bound, Cc, H, density_grid, count, n_marked)
+    n = int(n_marked.item())
+    return (n, count) if return_count else n
+
+
 # ---------------------------------------------------------------------------------------------
 # occupancy-grid path (cuda_ray=True): raymarching/raymarching.py:50-77, 160-380
 # ---------------------------------------------------------------------------------------------

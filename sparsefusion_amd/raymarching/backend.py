@@ -44,6 +44,18 @@ def packbits(grid, N, density_thresh, bitfield):
                                       _lib.stream_ptr()), "packbits")
 
 
+def occ_mark_untrained(poses, intrinsics, B, bound, C, H, density_grid, count, n_marked):
+    """density_grid [C, H^3] in place; count [C, H^3] int32 or None; n_marked [1] int32 (zeroed by the entry)."""
+    for t, n in ((poses, "poses"), (intrinsics, "intrinsics"), (density_grid, "density_grid")):
+        _f32(t, n)
+    _i32(n_marked, "n_marked")
+    if count is not None:
+        _i32(count, "count")
+    _lib.check(_lib.lib().sf_occ_mark_untrained(_lib.ptr(poses) if B else None, _lib.ptr(intrinsics) if B else None, int(B),
+                                                float(bound), int(C), int(H), _lib.ptr(density_grid), _lib.ptr(count),
+                                                _lib.ptr(n_marked), _lib.stream_ptr()), "occ_mark_untrained")
+
+
 def _i32(t, name):
     if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
         raise RuntimeError(f"{name} must be a contiguous int32 CUDA tensor")

@@ -65,6 +65,26 @@ class PinholeCameras(torch.nn.Module):
         return torch.bmm(cam - self.T[:, None], self.R.transpose(1, 2))
 
 
+def poses_from_cameras(cameras):
+    """(poses [B, 4, 4] camera-to-world, intrinsics [B, 4] = fx, fy, cx, cy) of a camera batch with `R`, `T`, `focal_length` and
+    `principal_point` (NDC units; X_cam = X_world @ R + T), in the form NeRFRenderer.mark_untrained_grid takes:
+    poses[:, :3, :3] = R, poses[:, :3, 3] = -T @ R^T (the camera centre), intrinsics = (fx, fy, 1 + |px|, 1 + |py|).  That is a
+    symmetric frustum which contains the image: a point with z_cam > 0 whose NDC x, y lie inside (-1, 1) passes
+    |x_cam| < cx / fx * z_cam and |y_cam| < cy / fy * z_cam.  The test reads |x|, |y| and z > 0 only, so the +X left / +Y up axis
+    convention does not matter."""
+    R, T = cameras.R.float(), cameras.T.float()
+    B = R.shape[0]
+    f = cameras.focal_length.float().reshape(B, -1)
+    pp = getattr(cameras, "principal_point", None)
+    pp = torch.zeros(B, 2, device=R.device) if pp is None else pp.float().reshape(B, -1)
+    poses = torch.zeros(B, 4, 4, dtype=torch.float32, device=R.device)
+    poses[:, :3, :3] = R
+    poses[:, :3, 3] = -torch.bmm(T[:, None], R.transpose(1, 2))[:, 0]
+    poses[:, 3, 3] = 1.0
+    intrinsics = torch.cat([f.expand(B, 2), 1.0 + pp.expand(B, 2).abs()], -1)
+    return poses, intrinsics.contiguous()
+
+
 def _xy_to_ray_bundle(cameras, xy_grid, min_depth, max_depth, n_pts_per_ray):
     """pytorch3d `_xy_to_ray_bundle`: xy_grid [N, ..., 2] -> RayBundle with spatial dims `...`."""
     N = xy_grid.shape[0]
