@@ -288,6 +288,11 @@ uint64_t sf_ngp_render_forward_workspace_bytes(uint32_t N, uint32_t T);
  * buffer untouched between the two calls. */
 uint64_t sf_ngp_render_cache_bytes(uint32_t N, uint32_t T);
 
+/* Kernel of the two field passes of sf_ngp_render_forward (and of the calls built on it): on = 1 the matrix-core kernel (the
+ * default: hidden layers on f32 MFMA, same bits as the other), on = 0 the lane-per-point kernel it is checked against, on < 0
+ * changes nothing.  Process-wide.  Returns the setting before the call. */
+int sf_ngp_field_mfma(int on);
+
 /* Lambertian-shaded render WITHOUT gradient of the same rays (NeRFRenderer.run, shading='lambertian'): first the stages of
  * sf_ngp_render_forward with no field cache (same arguments, same nears / fars / z_sorted / sigma_s / rgb_s = albedo / depth /
  * weights_sum, bit for bit), then per sorted sample the point min(max(o + d z, lo), hi), its finite-difference normal (the six

@@ -22,10 +22,12 @@
 #include "ngp_device.h"
 #include "ngp_field_lds.h"
 #include "ngp_bwd_mfma.h"
+#include "ngp_field_mfma.h"
 #include "ngp_composite_wave.h"
 #include "ngp_scatter_bin.h"
 #include "ngp_shade.h"
 #include <stdlib.h>
+#include <atomic>
 #include <mutex>
 
 struct GridLevels;  // gridencoder.hip
@@ -370,6 +372,21 @@ extern "C" uint64_t sf_ngp_render_workspace_bytes(uint32_t N, uint32_t T) {
 
 extern "C" uint64_t sf_ngp_render_forward_workspace_bytes(uint32_t N, uint32_t T) { return (uint64_t)10 * N * T * sizeof(float); }
 
+// Grid of k_ngp_field_mfma: 256 CUs x the two 256-thread workgroups its registers leave room for, every workgroup resident from the
+// start (a workgroup stages the weights once).  Render forward at 128 x 128 rays, 512 / 1024 / 2048 workgroups: 0.89 / 0.91 / 0.93 ms;
+// 256: 1.19 ms (profiles/ngp_field_mfma_ab.log).
+#ifndef FM_GRID_CAP
+#define FM_GRID_CAP 512u
+#endif
+// Which kernel runs the two field passes of sf_ngp_render_forward (and of everything built on it): 1 = k_ngp_field_mfma (the
+// default), 0 = k_ngp_field.  on < 0 only asks.  Returns the previous setting.  Process-wide.
+static std::atomic<int> g_field_mfma{1};
+extern "C" int sf_ngp_field_mfma(int on) {
+  const int was = g_field_mfma.load(std::memory_order_relaxed);
+  if (on >= 0) g_field_mfma.store(on ? 1 : 0, std::memory_order_relaxed);
+  return was;
+}
+
 extern "C" uint64_t sf_ngp_render_cache_bytes(uint32_t N, uint32_t T) {
   return ((uint64_t)2 * N * T * NGP_FEAT + (uint64_t)N * 2 * T) * sizeof(float);
 }
@@ -399,15 +416,33 @@ extern "C" int sf_ngp_render_forward(const sf_ngp_field* f, const float* rays_o,
   float* feat_c = field_cache;
   float* feat_f = field_cache ? field_cache + NT * NGP_FEAT : nullptr;
   uint32_t* perm = field_cache ? reinterpret_cast<uint32_t*>(field_cache + 2 * NT * NGP_FEAT) : nullptr;
-  k_ngp_field<0><<<gridp, 256, 0, st>>>(fp, lv, rays_o, rays_d, aabb, nears, fars, lin, u_coarse, nullptr, nullptr, P, T,
-                                        z_c, sig_c, rgb_c, feat_c);
+  // the two field passes: k_ngp_field_mfma (ngp_field_mfma.h; same bits, the hidden layers on the matrix cores), or the lane-per-point
+  // k_ngp_field it is checked against (sf_ngp_field_mfma(0))
+  const bool mfma = g_field_mfma.load(std::memory_order_relaxed) != 0;
+  FMArgs fm{};
+  fm.table = fp.table; fm.w0 = fp.w0; fm.b0 = fp.b0; fm.w1 = fp.w1; fm.b1 = fp.b1; fm.w2 = fp.w2; fm.b2 = fp.b2; fm.bound = fp.bound;
+  fm.lv = lv; fm.rays_o = rays_o; fm.rays_d = rays_d; fm.aabb = aabb; fm.nears = nears; fm.fars = fars; fm.P = P; fm.T = T;
+  const uint32_t gridm = sf_div_up(sf_div_up(P, FM_PTS), 4) < FM_GRID_CAP ? sf_div_up(sf_div_up(P, FM_PTS), 4) : FM_GRID_CAP;
+  const size_t ldsm = FM_LDS_FLOATS * sizeof(float);
+  if (mfma) {
+    fm.lin = lin; fm.u = u_coarse; fm.z_out = z_c; fm.sigma = sig_c; fm.rgb = rgb_c; fm.feat_out = feat_c;
+    k_ngp_field_mfma<0><<<gridm, 256, ldsm, st>>>(fm);
+  } else {
+    k_ngp_field<0><<<gridp, 256, 0, st>>>(fp, lv, rays_o, rays_d, aabb, nears, fars, lin, u_coarse, nullptr, nullptr, P, T,
+                                          z_c, sig_c, rgb_c, feat_c);
+  }
   SF_CHECK_LAUNCH("ngp_field_coarse");
   const uint32_t gridr = sf_div_up(N, 64);
   k_ngp_sample_fine<<<gridr, 64, 2 * T * 64 * sizeof(float), st>>>(z_c, sig_c, u_fine, u_fine_row_stride, nears, fars,
                                                                   N, T, z_f);
   SF_CHECK_LAUNCH("ngp_sample_fine");
-  k_ngp_field<1><<<gridp, 256, 0, st>>>(fp, lv, rays_o, rays_d, aabb, nears, fars, nullptr, nullptr, z_f, nullptr, P, T,
-                                        nullptr, sig_f, rgb_f, feat_f);
+  if (mfma) {
+    fm.lin = nullptr; fm.u = nullptr; fm.z_in = z_f; fm.z_out = nullptr; fm.sigma = sig_f; fm.rgb = rgb_f; fm.feat_out = feat_f;
+    k_ngp_field_mfma<1><<<gridm, 256, ldsm, st>>>(fm);
+  } else {
+    k_ngp_field<1><<<gridp, 256, 0, st>>>(fp, lv, rays_o, rays_d, aabb, nears, fars, nullptr, nullptr, z_f, nullptr, P, T,
+                                          nullptr, sig_f, rgb_f, feat_f);
+  }
   SF_CHECK_LAUNCH("ngp_field_fine");
   // one WAVE per ray: rank sort of cat([coarse, fine]) by readlane keys + scans (ngp_composite_wave.h)
   k_ngp_composite_wave<<<sf_div_up(N, 4), 256, 4 * 5 * 2 * T * sizeof(float), st>>>(

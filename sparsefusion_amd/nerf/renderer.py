@@ -77,6 +77,12 @@ class _FieldHandle:
 
 
 _FEAT_CACHE = True        # False: the backward re-gathers the features (the C ABI's field_cache = NULL path; tests flip this module attribute)
+_FIELD_MFMA = True        # False: the field passes run the lane-per-point k_ngp_field (same bits; the library's sf_ngp_field_mfma switch)
+
+
+def _select_field_kernel(lib):
+    """Hand `_FIELD_MFMA` to the library (process-wide there) before a call that runs the field passes."""
+    lib.sf_ngp_field_mfma(1 if _FIELD_MFMA else 0)
 
 
 class _RenderFn(torch.autograd.Function):
@@ -103,6 +109,7 @@ class _RenderFn(torch.autograd.Function):
         # grad mode is always off in here -- an eval render of a trainable field must not allocate / write the 268 MB cache
         if _FEAT_CACHE and grad_mode and any(ctx.needs_input_grad[13:]):
             cache = torch.empty(lib.sf_ngp_render_cache_bytes(N, T) // 4, **f32)
+        _select_field_kernel(lib)
         rc = lib.sf_ngp_render_forward(C.byref(f), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(aabb), N, T,
                                        float(min_near), _lib.ptr(lin), _lib.ptr(u_coarse), _lib.ptr(u_fine),
                                        int(u_stride), float(bg), _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(z_s),
@@ -408,6 +415,7 @@ class NeRFRenderer(nn.Module):
         wbytes = lib.sf_ngp_render_shaded_workspace_bytes(N, T)
         work = torch.empty(max(1, wbytes // 4), **f32)
         f = self._field_handle().struct(params)
+        _select_field_kernel(lib)
         rc = lib.sf_ngp_render_shaded_forward(C.byref(f), _lib.ptr(o), _lib.ptr(d), _lib.ptr(aabb), N, T, float(self.min_near),
                                               _lib.ptr(lin), _lib.ptr(u_coarse), _lib.ptr(u_fine), int(u_stride), bg, _lib.ptr(light),
                                               ratio, float(epsilon), _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(z_s), _lib.ptr(sig_s),
