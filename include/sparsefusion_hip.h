@@ -293,6 +293,13 @@ uint64_t sf_ngp_render_cache_bytes(uint32_t N, uint32_t T);
  * changes nothing.  Process-wide.  Returns the setting before the call. */
 int sf_ngp_field_mfma(int on);
 
+/* Kernel of the field backward of sf_ngp_render_backward when a field cache is passed: on = 1 the pipelined kernel
+ * (k_ngp_field_bwd_pipe: operands a trip ahead, the same values), on = 0 k_ngp_field_bwd_mfma, which it is checked against and which
+ * always runs the re-gather path (field_cache = NULL), on < 0 changes nothing.  Process-wide.  Returns the setting before the call. */
+int sf_ngp_field_bwd_pipe(int on);
+/* counts[0] / counts[1]: launches of k_ngp_field_bwd_mfma / k_ngp_field_bwd_pipe by this process so far (host memory). */
+void sf_ngp_field_bwd_launches(uint64_t* counts);
+
 /* Lambertian-shaded render WITHOUT gradient of the same rays (NeRFRenderer.run, shading='lambertian'): first the stages of
  * sf_ngp_render_forward with no field cache (same arguments, same nears / fars / z_sorted / sigma_s / rgb_s = albedo / depth /
  * weights_sum, bit for bit), then per sorted sample the point min(max(o + d z, lo), hi), its finite-difference normal (the six

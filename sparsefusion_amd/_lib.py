@@ -110,6 +110,8 @@ SIGNATURES = {
     "sf_ngp_render_forward_workspace_bytes": (u64, [u32, u32]),
     "sf_ngp_render_cache_bytes": (u64, [u32, u32]),
     "sf_ngp_field_mfma": (C.c_int, [C.c_int]),
+    "sf_ngp_field_bwd_pipe": (C.c_int, [C.c_int]),
+    "sf_ngp_field_bwd_launches": (None, [C.c_void_p]),
     "sf_ngp_render_shaded_forward": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, u32, u32, C.c_float, c_f32p, c_f32p,
                                                c_f32p, u32, C.c_float, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p,
                                                c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,

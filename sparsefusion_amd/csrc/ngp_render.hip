@@ -22,6 +22,7 @@
 #include "ngp_device.h"
 #include "ngp_field_lds.h"
 #include "ngp_bwd_mfma.h"
+#include "ngp_bwd_pipe.h"
 #include "ngp_field_mfma.h"
 #include "ngp_composite_wave.h"
 #include "ngp_scatter_bin.h"
@@ -387,6 +388,21 @@ extern "C" int sf_ngp_field_mfma(int on) {
   return was;
 }
 
+// Which kernel runs the field backward of sf_ngp_render_backward when the forward left a field cache: 1 = k_ngp_field_bwd_pipe
+// (ngp_bwd_pipe.h: the same values, operands a trip ahead), 0 = k_ngp_field_bwd_mfma.  Without a cache (the re-gather path) it is
+// always k_ngp_field_bwd_mfma.  on < 0 only asks.  Returns the previous setting.  Process-wide.
+static std::atomic<int> g_field_bwd_pipe{SF_FIELD_BWD_PIPE_DEFAULT};
+static std::atomic<uint64_t> g_field_bwd_launches[2];      // launches of [0] k_ngp_field_bwd_mfma, [1] k_ngp_field_bwd_pipe
+extern "C" int sf_ngp_field_bwd_pipe(int on) {
+  const int was = g_field_bwd_pipe.load(std::memory_order_relaxed);
+  if (on >= 0) g_field_bwd_pipe.store(on ? 1 : 0, std::memory_order_relaxed);
+  return was;
+}
+extern "C" void sf_ngp_field_bwd_launches(uint64_t* counts) {
+  counts[0] = g_field_bwd_launches[0].load(std::memory_order_relaxed);
+  counts[1] = g_field_bwd_launches[1].load(std::memory_order_relaxed);
+}
+
 extern "C" uint64_t sf_ngp_render_cache_bytes(uint32_t N, uint32_t T) {
   return ((uint64_t)2 * N * T * NGP_FEAT + (uint64_t)N * 2 * T) * sizeof(float);
 }
@@ -574,6 +590,7 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   static unsigned attr_mask = 0;
   if (dev_id >= 32 || !(attr_mask & (1u << dev_id))) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc) != hipSuccess)
       SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot raise the dynamic LDS limits");
     if (dev_id < 32) attr_mask |= 1u << dev_id;
@@ -672,8 +689,12 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
     a.perm = field_cache ? reinterpret_cast<const uint32_t*>(field_cache + 2 * (size_t)N * T * NGP_FEAT) : nullptr;
     const uint32_t trips = sf_div_up(Pc, FB_PTS);
     const uint32_t grid = trips < 1024 ? sf_div_up(trips, 4) : 256;   // one resident workgroup per CU (LDS-bound), 4 waves each
-    k_ngp_field_bwd_mfma<<<grid, 256, lds2, st>>>(a);
-    SF_CHECK_LAUNCH("ngp_field_bwd_mfma");
+    // with a field cache: k_ngp_field_bwd_pipe (ngp_bwd_pipe.h; same trips, same LDS image, same values) unless switched off
+    const int pipe = field_cache && g_field_bwd_pipe.load(std::memory_order_relaxed) != 0 ? 1 : 0;
+    if (pipe) k_ngp_field_bwd_pipe<<<grid, 256, lds2, st>>>(a);
+    else k_ngp_field_bwd_mfma<<<grid, 256, lds2, st>>>(a);
+    SF_CHECK_LAUNCH(pipe ? "ngp_field_bwd_pipe" : "ngp_field_bwd_mfma");
+    g_field_bwd_launches[pipe].fetch_add(1, std::memory_order_relaxed);
     if (dfeat && last < lv.L) {
       hipStream_t sf = st;
       if (fork) {

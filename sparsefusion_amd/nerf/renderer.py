@@ -78,11 +78,17 @@ class _FieldHandle:
 
 _FEAT_CACHE = True        # False: the backward re-gathers the features (the C ABI's field_cache = NULL path; tests flip this module attribute)
 _FIELD_MFMA = True        # False: the field passes run the lane-per-point k_ngp_field (same bits; the library's sf_ngp_field_mfma switch)
+_FIELD_BWD_PIPE = True    # False: the cached field backward runs k_ngp_field_bwd_mfma (same values; the library's sf_ngp_field_bwd_pipe switch)
 
 
 def _select_field_kernel(lib):
     """Hand `_FIELD_MFMA` to the library (process-wide there) before a call that runs the field passes."""
     lib.sf_ngp_field_mfma(1 if _FIELD_MFMA else 0)
+
+
+def _select_field_bwd_kernel(lib):
+    """Hand `_FIELD_BWD_PIPE` to the library (process-wide there) before a call that runs the field backward."""
+    lib.sf_ngp_field_bwd_pipe(1 if _FIELD_BWD_PIPE else 0)
 
 
 class _RenderFn(torch.autograd.Function):
@@ -136,6 +142,7 @@ class _RenderFn(torch.autograd.Function):
         work = torch.empty(max(1, wbytes // 4), dtype=torch.float32, device=rays_o.device)
         g_image = (g_image if g_image is not None else torch.zeros(N, 3, device=rays_o.device)).contiguous().float()
         g_ws = g_ws.contiguous().float() if g_ws is not None else None
+        _select_field_bwd_kernel(lib)
         rc = lib.sf_ngp_render_backward(C.byref(f), C.byref(g), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(aabb), N, T,
                                         _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(z_s), _lib.ptr(sig_s), _lib.ptr(rgb_s),
                                         ctx.bg, _lib.ptr(g_image), _lib.ptr(g_ws), int(ctx.rays_per_row), _lib.ptr(cache),

@@ -1,7 +1,8 @@
 """Time the fused NGP render (forward, forward+backward) at the BASELINE size: 128x128 rays, 64+64 samples.
 --shading lambertian adds, after the default output: the shaded render (sf_ngp_render_shaded_forward), the albedo forward at the same
 size, and the composed route (albedo forward + sf_ngp_point_attrs over the sorted points + torch glue for the weights and the sums),
-each the median of 5 torch-event timings after a warm-up."""
+each the median of 5 torch-event timings after a warm-up.
+--bwd-pipe 0|1 selects the kernel of the cached field backward (renderer._FIELD_BWD_PIPE) instead of the default."""
 import os
 import sys
 import time
@@ -12,6 +13,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import ngp_ref  # noqa: E402  (parameter initialiser only)
 from sparsefusion_amd.nerf import NeRFNetwork, get_default_torch_ngp_opt  # noqa: E402
 
+if "--bwd-pipe" in sys.argv:
+    from sparsefusion_amd.nerf import renderer as _R
+    _R._FIELD_BWD_PIPE = sys.argv[sys.argv.index("--bwd-pipe") + 1] == "1"
+    print(f"field backward  : {'k_ngp_field_bwd_pipe' if _R._FIELD_BWD_PIPE else 'k_ngp_field_bwd_mfma'}")
 dev = "cuda:0"
 p = ngp_ref.init_params(bound=4, seed=1, table_std=0.5, sigma_bias=-3.0)
 net = NeRFNetwork(get_default_torch_ngp_opt())
