@@ -240,6 +240,38 @@ int sf_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t nz, float is
                void* workspace, uint64_t workspace_bytes, float* verts, int32_t* faces,
                void* stream);
 
+/* Connected components of an indexed triangle mesh (faces [F,3] i32, V vertices): two vertices are connected when a face names
+ * both -- by INDEX only, coincident but unwelded vertices stay apart.  Lock-free union-find on the device; the label of a
+ * component is the smallest vertex index in it, so the result is a function of the mesh alone.  A face with an index outside
+ * [0, V) is invalid: it connects nothing and is counted; a face with a repeated index is valid.  Outputs: vertex_label [V] (an
+ * unreferenced vertex is its own label), face_label [F] or NULL (-1 for an invalid face), faces_per_label [V] (0 where v is no
+ * label), counts3 = {components with at least one face, faces of the largest, invalid faces} on the device.
+ * SF_ERR_INVALID before any device call: V or F >= 2^31, a NULL required pointer (faces with F > 0; vertex_label,
+ * faces_per_label, workspace with V > 0; counts3), workspace below sf_mesh_components_workspace_bytes(V, F).  F == 0 or V == 0 is
+ * SF_OK: labels the identity, counts zero (with V == 0 every face is invalid). */
+uint64_t sf_mesh_components_workspace_bytes(uint32_t V, uint32_t F);
+int sf_mesh_components(const int32_t* faces, uint32_t F, uint32_t V, int32_t* vertex_label, int32_t* face_label,
+                       uint32_t* faces_per_label, uint32_t* counts3, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* Removal of small components, order preserved.  A component of n faces is kept iff n >= min_faces and
+ * n >= ceil(min_fraction * largest) (product in double); a face iff it is valid and its component is kept; a vertex iff a kept
+ * face names it.  sf_mesh_filter_count takes sf_mesh_components' vertex_label / faces_per_label / counts3 and writes
+ * counts2 = {V', F'}; sf_mesh_filter_emit (same faces and untouched workspace, after the count) writes out_verts [V',3] (bit
+ * copies), out_faces [F',3] (remapped), vertex_ids [V'] and face_ids [F'] (the old index of every kept row, strictly increasing).
+ * SF_ERR_INVALID before any device call: V or F >= 2^31, workspace below sf_mesh_filter_workspace_bytes(V, F), min_fraction not
+ * finite or outside [0, 1], and a NULL pointer among those the host can judge: faces with F > 0 and workspace (both entries);
+ * vertex_label and faces_per_label with V > 0, counts3, counts2 (count); verts with V > 0 (emit).  The four outputs of
+ * sf_mesh_filter_emit are NOT checked: each may be NULL when its count is 0, and the host does not know V' / F' there (it reads
+ * nothing back), so buffers of at least V' / F' rows are the caller's responsibility -- a NULL or short output with rows to write
+ * is a device fault, not an error code.  F == 0 or V == 0: V' = F' = 0. */
+uint64_t sf_mesh_filter_workspace_bytes(uint32_t V, uint32_t F);
+int sf_mesh_filter_count(const int32_t* faces, uint32_t F, uint32_t V, const int32_t* vertex_label,
+                         const uint32_t* faces_per_label, const uint32_t* counts3, uint32_t min_faces, double min_fraction,
+                         void* workspace, uint64_t workspace_bytes, uint32_t* counts2, void* stream);
+int sf_mesh_filter_emit(const float* verts, const int32_t* faces, uint32_t F, uint32_t V, void* workspace,
+                        uint64_t workspace_bytes, float* out_verts, int32_t* out_faces, int32_t* vertex_ids, int32_t* face_ids,
+                        void* stream);
+
 /* Full training/eval render of N rays with T coarse + T fine samples (T<=64).
  * lin [T] = linspace(0,1,T); u_coarse [N,T] in [0,1) or NULL (perturb=False);
  * u_fine: uniforms for the inverse-CDF draw, row n at u_fine + n*u_fine_row_stride

@@ -100,6 +100,12 @@ SIGNATURES = {
     "sf_mc_workspace_bytes": (u64, [u32, u32, u32]),
     "sf_mc_count": (C.c_int, [c_f32p, u32, u32, u32, C.c_float, C.c_void_p, u64, C.c_void_p, C.c_void_p]),
     "sf_mc_emit": (C.c_int, [c_f32p, u32, u32, u32, C.c_float, C.c_void_p, u64, c_f32p, c_i32p, C.c_void_p]),
+    "sf_mesh_components_workspace_bytes": (u64, [u32, u32]),
+    "sf_mesh_components": (C.c_int, [c_i32p, u32, u32, c_i32p, c_i32p, C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_void_p]),
+    "sf_mesh_filter_workspace_bytes": (u64, [u32, u32]),
+    "sf_mesh_filter_count": (C.c_int, [c_i32p, u32, u32, c_i32p, C.c_void_p, C.c_void_p, u32, C.c_double, C.c_void_p, u64,
+                                       C.c_void_p, C.c_void_p]),
+    "sf_mesh_filter_emit": (C.c_int, [c_f32p, c_i32p, u32, u32, C.c_void_p, u64, c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
     "sf_ngp_render_forward": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, u32, u32, C.c_float,
                                         c_f32p, c_f32p, c_f32p, u32, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p,
                                         c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, u64, C.c_void_p]),

@@ -1,9 +1,11 @@
 // Mesh export (NeRFRenderer.export_mesh, external/nerf/renderer_df.py:122-165; extract_fields / extract_geometry,
 // external/nerf/utils.py:174-204): the NGP density on a lattice, the separable Gaussian + volume statistics and marching cubes
 // of mesh_kernels.h, the point attributes of ngp_point_attrs.h and the texture bake of ngp_texture.h (the reference's _export,
-// renderer_df.py:166-306).  Host entry points declared in include/sparsefusion_hip.h.  See DESIGN.md section 9.
+// renderer_df.py:166-306), and the connected components / floater removal of mesh_clean.h (no counterpart in the reference, which
+// leaves clean-up to pymeshlab).  Host entry points declared in include/sparsefusion_hip.h.  See DESIGN.md section 9.
 #include "sf_common.h"
 #include "mesh_kernels.h"
+#include "mesh_clean.h"
 #include "ngp_field_lds.h"
 #include "ngp_point_attrs.h"
 #include "ngp_texture.h"
@@ -233,5 +235,124 @@ extern "C" int sf_mc_emit(const float* vol, uint32_t nx, uint32_t ny, uint32_t n
   SF_CHECK_LAUNCH("mc_emit_verts");
   k_mc_emit_faces<<<nb, MC_NT, 0, st>>>(d, w.code, w.boff, w.vbase, faces);
   SF_CHECK_LAUNCH("mc_emit_faces");
+  return SF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------- mesh clean-up
+// Connected components and floater removal (mesh_clean.h).
+static bool mcl_sizes_ok(uint32_t V, uint32_t F) { return V < (1u << 31) && F < (1u << 31); }
+
+extern "C" uint64_t sf_mesh_components_workspace_bytes(uint32_t V, uint32_t F) {
+  if (!mcl_sizes_ok(V, F)) return 0;
+  return align256((uint64_t)V * sizeof(uint32_t));      // parent u32 [V]
+}
+
+extern "C" int sf_mesh_components(const int32_t* faces, uint32_t F, uint32_t V, int32_t* vertex_label, int32_t* face_label,
+                                  uint32_t* faces_per_label, uint32_t* counts3, void* ws, uint64_t ws_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!mcl_sizes_ok(V, F)) SF_FAIL(SF_ERR_INVALID, "mesh_components: need V < 2^31 and F < 2^31");
+  if ((F && !faces) || (V && (!vertex_label || !faces_per_label || !ws)) || !counts3)
+    SF_FAIL(SF_ERR_INVALID, "mesh_components: null pointer");
+  if (ws_bytes < sf_mesh_components_workspace_bytes(V, F)) SF_FAIL(SF_ERR_INVALID, "mesh_components: workspace too small");
+  uint32_t* parent = (uint32_t*)ws;
+  const uint32_t gv = sf_grid_cap(sf_div_up(V, MCL_NT)), gf = sf_grid_cap(sf_div_up(F, MCL_NT));
+  k_cc_init<<<gv, MCL_NT, 0, st>>>(parent, faces_per_label, counts3, V);
+  SF_CHECK_LAUNCH("mesh_components init");
+  if (F && V) {
+    k_cc_hook<<<gf, MCL_NT, 0, st>>>(faces, F, V, parent);
+    SF_CHECK_LAUNCH("mesh_components hook");
+  }
+  if (V) {
+    k_cc_flatten<<<gv, MCL_NT, 0, st>>>(parent, V, vertex_label);
+    SF_CHECK_LAUNCH("mesh_components flatten");
+  }
+  if (F) {
+    k_cc_count<<<gf, MCL_NT, 0, st>>>(faces, F, V, vertex_label, face_label, faces_per_label, counts3);
+    SF_CHECK_LAUNCH("mesh_components count");
+  }
+  if (F && V) {
+    k_cc_stats<<<gv, MCL_NT, 0, st>>>(faces_per_label, V, counts3);
+    SF_CHECK_LAUNCH("mesh_components stats");
+  }
+  return SF_OK;
+}
+
+// Workspace: vert_keep u8 [V] | face_keep u8 [F] | remap u32 [V] | bsum u32 [2 * nblk] | boff u32 [2 * nblk]
+struct MclWs { uint8_t* vert_keep; uint8_t* face_keep; uint32_t* remap; uint32_t* bsum; uint32_t* boff; };
+
+static uint32_t mcl_blocks(uint32_t V, uint32_t F) {
+  const uint32_t n = V > F ? V : F;
+  return n ? sf_div_up(n, MC_BLOCK) : 1;
+}
+
+static MclWs mcl_ws(void* ws, uint32_t V, uint32_t F) {
+  const uint64_t nb = mcl_blocks(V, F);
+  char* b = (char*)ws;
+  MclWs w;
+  w.vert_keep = (uint8_t*)b;
+  b += align256(V);
+  w.face_keep = (uint8_t*)b;
+  b += align256(F);
+  w.remap = (uint32_t*)b;
+  b += align256((uint64_t)V * 4);
+  w.bsum = (uint32_t*)b;
+  b += align256(nb * 8);
+  w.boff = (uint32_t*)b;
+  return w;
+}
+
+extern "C" uint64_t sf_mesh_filter_workspace_bytes(uint32_t V, uint32_t F) {
+  if (!mcl_sizes_ok(V, F)) return 0;
+  return align256(V) + align256(F) + align256((uint64_t)V * 4) + 2 * align256((uint64_t)mcl_blocks(V, F) * 8);
+}
+
+static int mcl_filter_check(uint32_t V, uint32_t F, const int32_t* faces, void* ws, uint64_t ws_bytes, const char* what) {
+  if (!mcl_sizes_ok(V, F)) SF_FAIL(SF_ERR_INVALID, "%s: need V < 2^31 and F < 2^31", what);
+  if ((F && !faces) || !ws) SF_FAIL(SF_ERR_INVALID, "%s: null pointer", what);
+  if (ws_bytes < sf_mesh_filter_workspace_bytes(V, F)) SF_FAIL(SF_ERR_INVALID, "%s: workspace too small", what);
+  return SF_OK;
+}
+
+extern "C" int sf_mesh_filter_count(const int32_t* faces, uint32_t F, uint32_t V, const int32_t* vertex_label,
+                                    const uint32_t* faces_per_label, const uint32_t* counts3, uint32_t min_faces, double min_fraction,
+                                    void* ws, uint64_t ws_bytes, uint32_t* counts2, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mcl_filter_check(V, F, faces, ws, ws_bytes, "mesh_filter_count")) return rc;
+  if ((V && (!vertex_label || !faces_per_label)) || !counts3 || !counts2) SF_FAIL(SF_ERR_INVALID, "mesh_filter_count: null pointer");
+  if (!isfinite(min_fraction) || min_fraction < 0.0 || min_fraction > 1.0)
+    SF_FAIL(SF_ERR_INVALID, "mesh_filter_count: min_fraction must be finite and in [0, 1]");
+  const MclWs w = mcl_ws(ws, V, F);
+  const uint32_t nb = mcl_blocks(V, F);
+  if (V) {
+    k_flt_zero<<<sf_grid_cap(sf_div_up(V, MCL_NT)), MCL_NT, 0, st>>>(w.vert_keep, V);
+    SF_CHECK_LAUNCH("mesh_filter zero");
+  }
+  if (F) {
+    k_flt_flags<<<sf_grid_cap(sf_div_up(F, MCL_NT)), MCL_NT, 0, st>>>(faces, F, V, vertex_label, faces_per_label, counts3, min_faces,
+                                                                     min_fraction, w.face_keep, w.vert_keep);
+    SF_CHECK_LAUNCH("mesh_filter flags");
+  }
+  k_flt_bsum<<<nb, MC_NT, 0, st>>>(w.vert_keep, V, w.face_keep, F, w.bsum);
+  SF_CHECK_LAUNCH("mesh_filter block sums");
+  k_mc_scan<<<1, MC_NT, 0, st>>>(w.bsum, nb, w.boff, counts2);
+  SF_CHECK_LAUNCH("mesh_filter scan");
+  return SF_OK;
+}
+
+extern "C" int sf_mesh_filter_emit(const float* verts, const int32_t* faces, uint32_t F, uint32_t V, void* ws, uint64_t ws_bytes,
+                                   float* out_verts, int32_t* out_faces, int32_t* vertex_ids, int32_t* face_ids, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mcl_filter_check(V, F, faces, ws, ws_bytes, "mesh_filter_emit")) return rc;
+  if (V && !verts) SF_FAIL(SF_ERR_INVALID, "mesh_filter_emit: null pointer");
+  const MclWs w = mcl_ws(ws, V, F);
+  if (V) {
+    k_flt_emit_verts<<<sf_div_up(V, MC_BLOCK), MC_NT, 0, st>>>((const uint32_t*)verts, V, w.vert_keep, w.boff, (uint32_t*)out_verts,
+                                                              vertex_ids, w.remap);
+    SF_CHECK_LAUNCH("mesh_filter emit vertices");
+  }
+  if (F) {
+    k_flt_emit_faces<<<sf_div_up(F, MC_BLOCK), MC_NT, 0, st>>>(faces, F, w.face_keep, w.boff, w.remap, out_faces, face_ids);
+    SF_CHECK_LAUNCH("mesh_filter emit faces");
+  }
   return SF_OK;
 }

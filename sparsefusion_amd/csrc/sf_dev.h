@@ -145,6 +145,33 @@ static inline void sf_lds_barrier() { hipemu::syncthreads(); }
 #define SF_LGKM0() do { } while (0)
 #define SF_USE_FROM_HERE(x) do { } while (0)
 static inline void sf_glds_done() { if (sf_glds_lane[threadIdx.x].n) { fprintf(stderr, "LDS-DMA loads still in flight at kernel end\n"); abort(); } }
+// Integer atomics on global or LDS words (relaxed); each returns the old value.  The lanes of a workgroup are fibers that run one
+// after the other, so a lock-free loop would never see another lane act between its read and its compare-and-swap.  A harness may
+// set sf_emu_atomic_yield for kernels WITHOUT workgroup barriers: every atomic (the load included) is then preceded by a wave
+// rendezvous, so the lanes of a wave advance one atomic at a time, in alternating order.  The limit: only the 64 lanes of ONE wave
+// interleave.  hip_emu.h runs a wave to its end before the next wave and workgroups one after the other, so a word is never
+// contended across waves or workgroups under emulation; that contention is exercised on the GPU only.
+static bool sf_emu_atomic_yield = false;
+static inline void sf_emu_yield() { if (sf_emu_atomic_yield) hipemu::t_wave->bar.wait(); }
+static inline uint32_t sf_atomic_load_u32(const uint32_t* p) { sf_emu_yield(); return __atomic_load_n(p, __ATOMIC_RELAXED); }
+static inline uint32_t sf_atomic_add_u32(uint32_t* p, uint32_t v) { sf_emu_yield(); return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+static inline uint32_t sf_atomic_cas_u32(uint32_t* p, uint32_t expect, uint32_t desired) {
+  sf_emu_yield();
+  (void)__atomic_compare_exchange_n(p, &expect, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+  return expect;
+}
+static inline uint32_t sf_atomic_min_u32(uint32_t* p, uint32_t v) {
+  sf_emu_yield();
+  uint32_t old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+static inline uint32_t sf_atomic_max_u32(uint32_t* p, uint32_t v) {
+  sf_emu_yield();
+  uint32_t old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
 static const uint32_t sf_zero128[32] __attribute__((aligned(128))) = {0};
 #else
 #include <hip/hip_runtime.h>
@@ -217,6 +244,14 @@ SF_DEV void sf_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory")
 // this wave's LDS reads have returned, then the workgroup meets (a raw s_barrier: __syncthreads() would drain the LDS-DMA queue)
 SF_DEV void sf_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 SF_DEV void sf_glds_done() {}
+// Integer atomics on global or LDS words (relaxed, device scope); each returns the old value.  The load goes to the coherent level
+// (L2) like the read-modify-writes: a plain load may be served from the CU's vector cache and keep returning a word that another
+// CU has since replaced, which a lock-free retry loop must not depend on.
+SF_DEV uint32_t sf_atomic_load_u32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+SF_DEV uint32_t sf_atomic_add_u32(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+SF_DEV uint32_t sf_atomic_cas_u32(uint32_t* p, uint32_t expect, uint32_t desired) { return atomicCAS(p, expect, desired); }
+SF_DEV uint32_t sf_atomic_min_u32(uint32_t* p, uint32_t v) { return atomicMin(p, v); }
+SF_DEV uint32_t sf_atomic_max_u32(uint32_t* p, uint32_t v) { return atomicMax(p, v); }
 // scheduling hint: the next n instructions of class `mask` (0x008 MFMA, 0x100 LDS read) go here, in program order of the groups
 #define SF_SCHED_GROUP(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 #define SF_LGKM0() __builtin_amdgcn_s_waitcnt(0xc07f)      // lgkmcnt(0), visible to the compiler's own counting

@@ -1,7 +1,8 @@
 """Mesh export on the GPU: the NGP density on a lattice, PyMCubes' Gaussian smoothing, fp64 volume statistics and marching cubes
 (C ABI in include/sparsefusion_hip.h, kernels in csrc/mesh_kernels.h and csrc/mesh.hip), and per-vertex
 colour and normal from the field (sf_ngp_point_attrs, csrc/ngp_point_attrs.h) with OBJ / PLY writers that carry them, and a
-texture atlas baked from the field (sf_ngp_texture_bake, csrc/ngp_texture.h) with its OBJ / MTL / PNG writers.
+texture atlas baked from the field (sf_ngp_texture_bake, csrc/ngp_texture.h) with its OBJ / MTL / PNG writers, and mesh clean-up:
+connected components and floater removal (sf_mesh_components / sf_mesh_filter_*, csrc/mesh_clean.h).
 
 The functions take and return device tensors; numpy input is run on the current HIP device and comes back as numpy, as a `mcubes`
 user would expect.  There is no CPU path.
@@ -388,3 +389,135 @@ def export_obj_textured(vertices, faces, uvs, filename, mtl_name, normals=None):
             fh.write(("f %d/%d %d/%d %d/%d\n" * f.shape[0]) % tuple(np.stack([f, ti], -1).ravel().tolist()))
         else:
             fh.write(("f %d/%d/%d %d/%d/%d %d/%d/%d\n" * f.shape[0]) % tuple(np.stack([f, ti, f], -1).ravel().tolist()))
+
+
+# -------------------------------------------------------------------------------------------------------------------- clean-up
+# Connected components and floater removal (sf_mesh_components / sf_mesh_filter_*, csrc/mesh_clean.h).
+def _faces_device(faces, what, device=None):
+    """(int32 contiguous [F, 3] device tensor, came_from_numpy).  int64 indices outside int32 are clamped to -1 / 2^31 - 1 first,
+    which no vertex count reaches: they stay invalid."""
+    from_np = isinstance(faces, np.ndarray)
+    if not from_np and not isinstance(faces, torch.Tensor):
+        raise TypeError(f"{what}: faces: expected a torch tensor or a numpy array, got {type(faces).__name__}")
+    if faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: expected faces [F, 3], got shape {tuple(faces.shape)}")
+    if from_np:
+        if faces.dtype not in (np.int32, np.int64):
+            raise TypeError(f"{what}: faces must be int32 or int64, got {faces.dtype}")
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{what}: numpy input runs on the current HIP device and there is none (no CPU path)")
+        f = torch.tensor(faces).to(device or f"cuda:{torch.cuda.current_device()}")      # a copy: the array may be read-only
+    else:
+        if faces.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{what}: faces must be int32 or int64, got {faces.dtype}")
+        _lib.require_cuda(faces)
+        f = faces.detach()
+    if f.dtype == torch.int64:
+        f = f.clamp(-1, (1 << 31) - 1).to(torch.int32)
+    return f.contiguous(), from_np
+
+
+def _num_vertices(V, what):
+    if isinstance(V, bool) or not isinstance(V, (int, np.integer)):
+        raise TypeError(f"{what}: num_vertices must be an int, got {type(V).__name__}")
+    if not 0 <= int(V) < 1 << 31:
+        raise ValueError(f"{what}: need 0 <= num_vertices < 2^31, got {V}")
+    return int(V)
+
+
+def _components(f, V):
+    """sf_mesh_components on f [F, 3] int32 (device, contiguous) -> vertex_label, face_label, faces_per_label, counts3 (device)"""
+    F, dev = f.shape[0], f.device
+    if F >= 1 << 31:
+        raise ValueError(f"connected_components: need F < 2^31, got {F}")
+    lib = _lib.lib()
+    i32 = dict(dtype=torch.int32, device=dev)
+    vertex_label, face_label, per = torch.empty(V, **i32), torch.empty(F, **i32), torch.empty(V, **i32)
+    counts3 = torch.empty(3, **i32)
+    wbytes = lib.sf_mesh_components_workspace_bytes(V, F)
+    work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    pz = lambda t: _lib.ptr(t if t.numel() else None)      # noqa: E731
+    rc = lib.sf_mesh_components(pz(f), F, V, pz(vertex_label), pz(face_label), pz(per), _lib.ptr(counts3), pz(work), wbytes,
+                                _lib.stream_ptr())
+    _lib.check(rc, "mesh_components")
+    return vertex_label, face_label, per, counts3
+
+
+def connected_components(faces, num_vertices):
+    """Connected components of an indexed triangle mesh on the GPU: faces [F, 3] int32 (or int64) and the vertex count ->
+    dict of vertex_label [V] int32, face_label [F] int32, faces_per_label [V] int32 (device tensors; numpy for numpy input) and the
+    ints n_components, largest (face count of the largest component) and n_invalid (one read of three words).
+
+    Two vertices are connected when a face names both.  Connectivity is by INDEX only: coincident but unwelded vertices are not
+    merged (marching_cubes welds; a mesh read from a triangle soup does not).  The label of a component is the smallest vertex
+    index in it, so the result is a function of the mesh alone (lock-free union-find, csrc/mesh_clean.h).  A face with an index
+    outside [0, num_vertices), negative ones included, is invalid: it connects nothing, has face_label -1, belongs to no component
+    and is counted in n_invalid.  A degenerate face with a repeated index is valid and connects what it names.  An unreferenced
+    vertex is its own label with zero faces; faces_per_label is zero wherever v is not a label.  n_components counts the labels
+    with at least one face."""
+    V = _num_vertices(num_vertices, "connected_components")
+    f, from_np = _faces_device(faces, "connected_components")
+    vertex_label, face_label, per, counts3 = _components(f, V)
+    n_components, largest, n_invalid = (int(c) for c in counts3.cpu())
+    out = dict(vertex_label=vertex_label, face_label=face_label, faces_per_label=per)
+    if from_np:
+        out = {k: t.cpu().numpy() for k, t in out.items()}
+    out.update(n_components=n_components, largest=largest, n_invalid=n_invalid)
+    return out
+
+
+def clean_mesh(vertices, faces, min_faces=8, min_fraction=0.0):
+    """Floater removal on the GPU: drops every connected component (connected_components: by index, no welding) of fewer than
+    min_faces faces or fewer than ceil(min_fraction * largest) faces (product in double; min_fraction = 1 keeps only the components
+    tied for largest), every face that is invalid or belongs to a dropped component, and every vertex no kept face names
+    (unreferenced vertices go too).  Returns (vertices' [V', 3] float32 -- bit copies of the kept rows --, faces' [F', 3] int32 with
+    the indices remapped, vertex_ids [V'] int32, face_ids [F'] int32: the old index of every kept row).  Order is preserved:
+    vertex_ids and face_ids are strictly increasing.  Device tensors in -> device tensors out; numpy in -> numpy out.  One
+    device-to-host read of {V', F'} sizes the outputs.
+
+    min_faces = 8 is the default of the `clean_mesh` step the torch-ngp / stable-dreamfusion lineage runs after marching cubes -- a
+    choice of this library, not reference behaviour (the reference exports the raw mesh).  That step's other rule, pymeshlab's
+    diameter threshold, is not reproduced; neither are welding, smoothing, remeshing or decimation."""
+    if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)):
+        raise TypeError(f"clean_mesh: min_faces must be an int, got {type(min_faces).__name__}")
+    if not 0 <= int(min_faces) < 1 << 32:
+        raise ValueError(f"clean_mesh: need 0 <= min_faces < 2^32, got {min_faces}")
+    frac = float(min_fraction)
+    if not (np.isfinite(frac) and 0.0 <= frac <= 1.0):
+        raise ValueError(f"clean_mesh: min_fraction must be finite and in [0, 1], got {min_fraction!r}")
+    from_np = isinstance(vertices, np.ndarray)
+    if not from_np and not isinstance(vertices, torch.Tensor):
+        raise TypeError(f"clean_mesh: vertices: expected a torch tensor or a numpy array, got {type(vertices).__name__}")
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"clean_mesh: expected vertices [V, 3], got shape {tuple(vertices.shape)}")
+    if vertices.dtype != (np.float32 if from_np else torch.float32):
+        raise TypeError(f"clean_mesh: vertices must be float32 (the kept rows are bit copies), got {vertices.dtype}")
+    if isinstance(faces, np.ndarray) != from_np:
+        raise TypeError("clean_mesh: vertices and faces must both be torch tensors or both numpy arrays")
+    if from_np:
+        f, _ = _faces_device(faces, "clean_mesh")
+        v = torch.tensor(vertices).to(f.device)
+    else:
+        _lib.require_cuda(vertices)
+        f, _ = _faces_device(faces, "clean_mesh")
+        v = vertices.detach().contiguous()
+        if f.device != v.device:
+            raise ValueError(f"clean_mesh: vertices are on {v.device}, faces on {f.device}")
+    V, F, dev = _num_vertices(v.shape[0], "clean_mesh"), f.shape[0], v.device
+    vertex_label, _, per, counts3 = _components(f, V)
+    lib = _lib.lib()
+    wbytes = lib.sf_mesh_filter_workspace_bytes(V, F)
+    work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    counts2 = torch.empty(2, dtype=torch.int32, device=dev)
+    pz = lambda t: _lib.ptr(t if t.numel() else None)      # noqa: E731
+    st = _lib.stream_ptr()
+    _lib.check(lib.sf_mesh_filter_count(pz(f), F, V, pz(vertex_label), pz(per), _lib.ptr(counts3), int(min_faces), frac, _lib.ptr(work),
+                                        wbytes, _lib.ptr(counts2), st), "mesh_filter_count")
+    V2, F2 = (int(c) for c in counts2.cpu())
+    out_v = torch.empty(V2, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(F2, 3, dtype=torch.int32, device=dev)
+    vertex_ids, face_ids = torch.empty(V2, dtype=torch.int32, device=dev), torch.empty(F2, dtype=torch.int32, device=dev)
+    _lib.check(lib.sf_mesh_filter_emit(pz(v), pz(f), F, V, _lib.ptr(work), wbytes, pz(out_v), pz(out_f), pz(vertex_ids), pz(face_ids), st),
+               "mesh_filter_emit")
+    out = (out_v, out_f, vertex_ids, face_ids)
+    return tuple(t.cpu().numpy() for t in out) if from_np else out

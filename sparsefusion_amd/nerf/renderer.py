@@ -252,6 +252,42 @@ class NeRFRenderer(nn.Module):
         mesh.write_png(os.path.join(path, 'albedo.png'), texture)
         return world, faces, torch.from_numpy(uvs).to(world.device), texture
 
+    @torch.no_grad()
+    def export_mesh_cleaned(self, path, resolution=None, S=128, min_faces=8, min_fraction=0.0, epsilon=None, texture_size=None):
+        """export_mesh_attributes without the floaters: the same lattice, smoothing, level and marching cubes, then
+        mesh.clean_mesh -- every connected component (by vertex index; marching_cubes welds) of fewer than `min_faces` faces or
+        fewer than ceil(min_fraction * largest) faces is dropped with its vertices, order preserved.  The kept vertices are a subset
+        of export_mesh's bit for bit; their colours and normals (mesh.vertex_attributes on the kept vertices, `epsilon` as in
+        export_mesh_attributes) equal export_mesh_attributes' rows.  Writes `path/mcubes_mesh_clean.obj` (index coordinates, as
+        export_mesh writes them; `v x y z r g b`, `vn`, `f a//a ..`) and `path/mcubes_mesh_clean.ply` (binary, world coordinates).
+        With `texture_size` also the `mesh.obj` / `mesh.mtl` / `albedo.png` trio of export_mesh_textured, built from the cleaned
+        mesh: the shells no longer take atlas cells, so the chart edge of the remaining faces does not shrink.  Returns
+        (vertices [V', 3] in world coordinates, faces [F', 3] int32, colors [V', 3], normals [V', 3], vertex_ids [V'] int32 = the
+        index of every kept vertex in export_mesh's).
+
+        A sparse-view field almost always carries floaters, and marching cubes turns each into a small closed shell next to the
+        object.  min_faces = 8 is the default of the `clean_mesh` step the torch-ngp / stable-dreamfusion lineage runs after
+        marching cubes -- a choice of this library, not reference behaviour: the reference exports the raw mesh, and pymeshlab's
+        diameter rule is not reproduced.  `S` as in export_mesh."""
+        from .. import mesh
+        R = 128 if resolution is None else int(resolution)
+        raw_vertices, raw_faces, raw_world = self._mesh_geometry(R)
+        vertices, faces, vertex_ids, _ = mesh.clean_mesh(raw_vertices, raw_faces, min_faces=min_faces, min_fraction=min_fraction)
+        world = raw_world[vertex_ids.long()]                           # export_mesh's own rows: nothing is computed twice
+        colors, normals = mesh.vertex_attributes(self, world, 2.0 * self.bound / (R - 1) if epsilon is None else epsilon)
+        os.makedirs(path, exist_ok=True)
+        mesh.export_obj(vertices, faces, os.path.join(path, 'mcubes_mesh_clean.obj'), colors=colors, normals=normals)
+        mesh.export_ply(world, faces, os.path.join(path, 'mcubes_mesh_clean.ply'), colors=colors, normals=normals)
+        if texture_size is not None:
+            W = int(texture_size)
+            uvs = mesh.atlas_uv(faces.shape[0], W)
+            texture = mesh.bake_texture(self, world, faces, W)["rgb8"]
+            mesh.export_obj_textured(world, faces, uvs, os.path.join(path, 'mesh.obj'), 'mesh.mtl', normals=normals)
+            with open(os.path.join(path, 'mesh.mtl'), 'w') as fh:
+                fh.write(mesh.MTL_TEXT)
+            mesh.write_png(os.path.join(path, 'albedo.png'), texture)
+        return world, faces, colors, normals, vertex_ids
+
     def _mesh_geometry(self, R):
         """(vertices in index coordinates, faces, vertices in world coordinates) of the R^3 lattice"""
         from .. import mesh

@@ -2,13 +2,17 @@
 next to the CPU pipeline it is tested against (scipy gaussian_filter + numpy level + tests/mesh_ref.py marching cubes) on the
 same field.  One JSON line per resolution.
 
-    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu] [--attrs] [--texture]
+    python tools/mesh_time.py --res 128 256 [--reps 5] [--no-cpu] [--attrs] [--texture] [--clean]
 
 --attrs adds, per resolution and for a fixed set of 2^20 random points, the one-launch vertex attributes (sf_ngp_point_attrs) next to
 the same quantities composed from seven sf_ngp_density calls and torch glue (what the field API offered before that entry point).
 
 --texture adds, per resolution, the one-launch texture bake of the exported mesh (sf_ngp_texture_bake, 8-bit output) at 1024^2 and
 2048^2 next to the composed route: a point buffer built by torch from the atlas layout, sf_ngp_density on it, torch quantisation.
+
+--clean adds, per resolution, the clean-up stage on the exported mesh (mesh.clean_mesh: connected components, filter count, the read
+of {V', F'}, emit; and the two halves through the C ABI) next to the wall time of the scipy + numpy restatement the tests compare it
+with (tests/mesh_clean_common.py), and after the resolutions one line for the synthetic 1.1 M-face case of the tests.
 """
 import argparse
 import json
@@ -139,6 +143,45 @@ def texture_time(net, verts, faces, W, reps):
                 composed_ms=_median_ms(composed, reps))
 
 
+def clean_time(verts, faces, reps, min_faces=8, min_fraction=0.0):
+    """ms of mesh.clean_mesh (with its read-back), of sf_mesh_components and of sf_mesh_filter_count + emit on their own (events
+    around the C entries, outputs sized for the full mesh so that no read-back sits inside), and the wall ms of the CPU restatement"""
+    import mesh_clean_common as mcc
+    from sparsefusion_amd import _lib
+    lib = _lib.lib()
+    V, F, dev = int(verts.shape[0]), int(faces.shape[0]), verts.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    vl, fl, per, c3, c2 = (torch.empty(n, **i32) for n in (V, F, V, 3, 2))
+    wc, wf = lib.sf_mesh_components_workspace_bytes(V, F), lib.sf_mesh_filter_workspace_bytes(V, F)
+    ws_c, ws_f = (torch.empty(n, dtype=torch.uint8, device=dev) for n in (wc, wf))
+    ov, of, vi, fi = torch.empty(V, 3, device=dev), torch.empty(F, 3, **i32), torch.empty(V, **i32), torch.empty(F, **i32)
+    P, st = _lib.ptr, _lib.stream_ptr()
+
+    def components():
+        _lib.check(lib.sf_mesh_components(P(faces), F, V, P(vl), P(fl), P(per), P(c3), P(ws_c), wc, st))
+
+    def filt():
+        _lib.check(lib.sf_mesh_filter_count(P(faces), F, V, P(vl), P(per), P(c3), min_faces, min_fraction, P(ws_f), wf, P(c2), st))
+        _lib.check(lib.sf_mesh_filter_emit(P(verts), P(faces), F, V, P(ws_f), wf, P(ov), P(of), P(vi), P(fi), st))
+
+    out = dict(V=V, F=F, min_faces=min_faces, min_fraction=min_fraction,
+               clean_mesh_ms=_median_ms(lambda: mesh.clean_mesh(verts, faces, min_faces, min_fraction), reps),
+               components_ms=_median_ms(components, reps), filter_count_emit_ms=_median_ms(filt, reps))
+    n_comp, largest, n_invalid = (int(x) for x in c3.cpu())
+    V2, F2 = (int(x) for x in c2.cpu())
+    out.update(n_components=n_comp, largest=largest, n_invalid=n_invalid, V_kept=V2, F_kept=F2)
+    vh, fh = verts.cpu().numpy(), faces.cpu().numpy()
+    cpu = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        ref = mcc.reference_components(fh, V)
+        t1 = time.perf_counter()
+        mcc.reference_clean(vh, fh, V, ref, min_faces, min_fraction)
+        cpu.append(((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
+    out["cpu_scipy_components_ms"], out["cpu_numpy_filter_ms"] = (statistics.median(c[k] for c in cpu) for k in (0, 1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, nargs="+", default=[128, 256])
@@ -146,6 +189,7 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--attrs", action="store_true")
     ap.add_argument("--texture", action="store_true")
+    ap.add_argument("--clean", action="store_true")
     a = ap.parse_args()
     golden = torch.load(os.path.join(ROOT, "tests", "golden", "ngp_render.pt"))
     p = params_from_cfg(golden["teacher"]["cfg"])
@@ -184,6 +228,10 @@ def main():
             with torch.no_grad():
                 verts, faces = net.export_mesh(tmp, resolution=R)
                 out["texture"] = [texture_time(net, verts.contiguous(), faces, W, a.reps) for W in (1024, 2048)]
+        if a.clean:
+            with torch.no_grad():
+                verts, faces = net.export_mesh(tmp, resolution=R)
+                out["clean"] = clean_time(verts.contiguous(), faces, a.reps)
         if not a.no_cpu:
             v = vol.cpu().numpy()
             t0 = time.perf_counter()
@@ -196,6 +244,11 @@ def main():
             out["cpu_ms"] = dict(gaussian=(t1 - t0) * 1e3, stats=(t2 - t1) * 1e3, marching_cubes=(t3 - t2) * 1e3)
             out["cpu_V"], out["cpu_F"] = int(cv.shape[0]), int(cf.shape[0])
         print(json.dumps(out), flush=True)
+    if a.clean:
+        import mesh_clean_common as mcc
+        c = mcc.make_case(mcc.BIG_CASE)
+        verts, faces = torch.tensor(c["vertices"]).to("cuda:0"), torch.tensor(c["faces"]).to("cuda:0")
+        print(json.dumps(dict(case="synthetic strips, permuted numbering", clean=clean_time(verts, faces, a.reps))), flush=True)
 
 
 if __name__ == "__main__":
