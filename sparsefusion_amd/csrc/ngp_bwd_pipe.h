@@ -21,6 +21,8 @@
 //     relu(H1) and relu(H2) stay in the registers that produced them, so the masks of E and G read no LDS.
 //   db1 / db0 keep their VALU chains (point-ascending adds), with the 32 reads of a chain issued together.
 // No workgroup barrier in the loop and no spin-wait: the four waves of a workgroup never exchange data.
+// The phases share two GEMM shapes, each written once below: the row GEMM (fp_row_*: B1, B2, C, E, G, I) and the points GEMM
+// (fp_point_frags / fp_points_gemm: D, F, H); fp_store_dfeat is I's epilogue, fp_flush the flush after the last trip.
 #pragma once
 #include "ngp_bwd_mfma.h"                          // FBArgs and the LDS image (FB_*)
 
@@ -55,6 +57,115 @@ SF_DEV void fp_load(const FBArgs& a, uint32_t pc, uint32_t src, int half, FPOps&
   for (int i = 0; i < 3; ++i) { q.o[i] = a.rays_o[n * 3 + i]; q.d[i] = a.rays_d[n * 3 + i]; }
   q.g0 = half == 0 ? a.dsig[pc] : a.drgb[(size_t)pc * 3 + 1];
   q.g1 = half == 0 ? a.drgb[(size_t)pc * 3] : a.drgb[(size_t)pc * 3 + 2];
+}
+
+// ---- the two GEMM shapes of the kernel, on fragments of v_mfma_f32_16x16x4_f32: lane (li, kq) holds A[li][4s + kq] and B[4s + kq][li] of
+// k-step s and rows 4 kq + r, column li of a 16 x 16 accumulator tile.  Every helper is reached by all 64 lanes (sf_mfma4 is a rendezvous
+// of the wave under the emulation) and loads, multiplies and stores in fully unrolled loops: the arrays are registers.
+//
+// Row GEMM  c[mt][nt] = T[32][4 KS] B[4 KS][16 NT]  (+ the accumulators' initial value), T a wave-private tile of row stride ld: the A
+// fragments of both 16-row halves, av[mt][s] = T[mt * 16 + li][4 s + kq]
+template <int KS>
+SF_DEV void fp_row_frags(const float* T, int ld, int li, int kq, float (&av)[2][KS]) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    av[0][s] = T[li * ld + 4 * s + kq];
+    av[1][s] = T[(16 + li) * ld + 4 * s + kq];
+  }
+}
+// the k-steps ascending into every accumulator; b(s, nt) is the B fragment: a register the caller loaded, or an LDS read
+template <int KS, int NT, class BSrc>
+SF_DEV void fp_row_gemm(const float (&av)[2][KS], BSrc b, f32x4 (&c)[2][NT]) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const float bv = b(s, nt);
+      c[0][nt] = sf_mfma4(av[0][s], bv, c[0][nt]);
+      c[1][nt] = sf_mfma4(av[1][s], bv, c[1][nt]);
+    }
+}
+template <int NT>
+SF_DEV void fp_row_fill(f32x4 (&c)[2][NT], const float* v) {        // every row of column tile nt starts at v[nt] (a bias)
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) { c[0][nt] = f32x4{v[nt], v[nt], v[nt], v[nt]}; c[1][nt] = c[0][nt]; }
+}
+// the accumulator layout back into a tile: D[mt * 16 + 4 kq + r][nt * 16 + li] = val(mt, nt, r)
+SF_DEV int fp_row_at(int ld, int li, int kq, int mt, int nt, int r) { return (mt * 16 + 4 * kq + r) * ld + nt * 16 + li; }
+template <int NT, class Val>
+SF_DEV void fp_row_store(float* D, int ld, int li, int kq, Val val) {
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) D[fp_row_at(ld, li, kq, mt, nt, r)] = val(mt, nt, r);
+}
+// Points GEMM  acc[jt][kt] += sum over the 4 KS points of T  A[p][16 jt ..] (x) B[p][16 kt ..], the points ascending into the running
+// accumulator: the fragments v[s][t] = T[4 s + kq][t * 16 + li] of a block of points (T points at the block's first row)
+template <int KS, int NT>
+SF_DEV void fp_point_frags(const float* T, int ld, int li, int kq, float (&v)[KS][NT]) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) v[s][t] = T[(4 * s + kq) * ld + t * 16 + li];
+}
+template <int KS, int JT, int KT>
+SF_DEV void fp_points_gemm(const float (&av)[KS][JT], const float (&bv)[KS][KT], f32x4 (&acc)[JT][KT]) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s)
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt) acc[jt][kt] = sf_mfma4(av[s][jt], bv[s][kt], acc[jt][kt]);
+}
+
+// d(feat) of the trip at point p0, transposed through the F tile into the level-major [L][P][2] image, as k_ngp_field_bwd_mfma: lane =
+// (level lane >> 2, quarter lane & 3) owns 8 consecutive points of one level = 64 contiguous bytes
+SF_DEV void fp_store_dfeat(const FBArgs& a, const float* F, uint32_t p0, int lane) {
+  const uint32_t l = lane >> 2, q0 = (lane & 3) * 8;
+  if (l >= a.lv.L) return;
+  float* dst = a.dfeat_out + ((size_t)l * a.dfeat_P + a.p_off + p0 + q0) * 2;
+  if (p0 + FB_PTS <= a.P && !((a.dfeat_P | a.p_off) & 1)) {      // whole trip, 16-byte aligned rows
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x4 v;
+      v[0] = F[(q0 + 2 * j) * FB_SF + 2 * l];     v[1] = F[(q0 + 2 * j) * FB_SF + 2 * l + 1];
+      v[2] = F[(q0 + 2 * j + 1) * FB_SF + 2 * l]; v[3] = F[(q0 + 2 * j + 1) * FB_SF + 2 * l + 1];
+      *reinterpret_cast<f32x4*>(dst + 4 * j) = v;
+    }
+  } else {                                         // ragged last trip (or an odd point count)
+    for (int j = 0; j < 8; ++j)
+      if (p0 + q0 + j < a.P) { dst[2 * j] = F[(q0 + j) * FB_SF + 2 * l]; dst[2 * j + 1] = F[(q0 + j) * FB_SF + 2 * l + 1]; }
+  }
+}
+
+// this wave's gradient tiles as fixed-point integer adds: the same addends as k_ngp_field_bwd_mfma's waves
+SF_DEV void fp_flush(const FBArgs& a, int lane, const f32x4 (&acc1)[4][4], const f32x4 (&acc0)[4][2], const f32x4 (&acc2)[1][4], const f32x4& accb2,
+                     float accb1, float accb0) {
+  const int li = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = jt * 16 + 4 * kq + r;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) sf_grad_add(a.g_w1 + j * NGP_HID + kt * 16 + li, a.f_w1 + j * NGP_HID + kt * 16 + li, acc1[jt][kt][r], a.thr);
+      sf_grad_add(a.g_w0 + j * NGP_FEAT + li, a.f_w0 + j * NGP_FEAT + li, acc0[jt][0][r], a.thr);
+      sf_grad_add(a.g_w0 + j * NGP_FEAT + 16 + li, a.f_w0 + j * NGP_FEAT + 16 + li, acc0[jt][1][r], a.thr);
+    }
+  if (kq == 0) {
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sf_grad_add(a.g_w2 + r * NGP_HID + kt * 16 + li, a.f_w2 + r * NGP_HID + kt * 16 + li, acc2[0][kt][r], a.thr);
+    if (li == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sf_grad_add(a.g_b2 + r, a.f_b2 + r, accb2[r], a.thr);
+    }
+  }
+  sf_grad_add(a.g_b1 + lane, a.f_b1 + lane, accb1, a.thr);
+  sf_grad_add(a.g_b0 + lane, a.f_b0 + lane, accb0, a.thr);
 }
 
 // Requires the field cache (a.feat_c, a.feat_f, a.perm); the re-gather path is k_ngp_field_bwd_mfma's.
@@ -106,17 +217,18 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
     bb0[nt] = W[FB_B0 + nt * 16 + li];
     bb1[nt] = W[FB_B1 + nt * 16 + li];
   }
-  const float cb2 = li < NGP_OUT ? W[FB_B2 + (li & 3)] : 0.0f;
+  const float cb2[1] = {li < NGP_OUT ? W[FB_B2 + (li & 3)] : 0.0f};
+  const float zero4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 
   f32x4 acc1[4][4], acc0[4][2];                        // dW1[jt][kt], dW0[jt][ft] tiles (rows j = jt*16 + 4*kq + r, cols li)
-  f32x4 acc2[4], accb2 = f32x4{0.f, 0.f, 0.f, 0.f};    // lanes kq == 0: dW2[o = r][k = kt*16 + li]; db2[o = r] (the same in every column)
+  f32x4 acc2[1][4], accb2 = f32x4{0.f, 0.f, 0.f, 0.f}; // lanes kq == 0: dW2[o = r][k = kt*16 + li]; db2[o = r] (the same in every column)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     acc0[i][0] = f32x4{0.f, 0.f, 0.f, 0.f};
     acc0[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc2[0][i] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   float accb1 = 0.0f, accb0 = 0.0f;                    // db1[lane], db0[lane]
 
@@ -166,89 +278,38 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
     // ---- B1: H1 = relu(F W0^T + b0)
     {
       float av[2][NGP_FEAT / 4], bv[NGP_FEAT / 4][4];
-#pragma unroll
-      for (int s = 0; s < NGP_FEAT / 4; ++s) {
-        av[0][s] = F[li * FB_SF + 4 * s + kq];
-        av[1][s] = F[(16 + li) * FB_SF + 4 * s + kq];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) bv[s][nt] = W[FB_W0 + (nt * 16 + li) * FB_SF + 4 * s + kq];
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) { h1r[0][nt] = f32x4{bb0[nt], bb0[nt], bb0[nt], bb0[nt]}; h1r[1][nt] = h1r[0][nt]; }
+      fp_row_frags(F, FB_SF, li, kq, av);
 #pragma unroll
       for (int s = 0; s < NGP_FEAT / 4; ++s)
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          h1r[0][nt] = sf_mfma4(av[0][s], bv[s][nt], h1r[0][nt]);
-          h1r[1][nt] = sf_mfma4(av[1][s], bv[s][nt], h1r[1][nt]);
-        }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            h1r[mt][nt][r] = fmaxf(h1r[mt][nt][r], 0.0f);
-            H1[(mt * 16 + 4 * kq + r) * FB_SH + nt * 16 + li] = h1r[mt][nt][r];
-          }
+        for (int nt = 0; nt < 4; ++nt) bv[s][nt] = W[FB_W0 + (nt * 16 + li) * FB_SF + 4 * s + kq];
+      fp_row_fill(h1r, bb0);
+      fp_row_gemm(av, [&](int s, int nt) { return bv[s][nt]; }, h1r);
+      fp_row_store<4>(H1, FB_SH, li, kq, [&](int mt, int nt, int r) { return h1r[mt][nt][r] = fmaxf(h1r[mt][nt][r], 0.0f); });
     }
     sf_wave_sync();
     // ---- B2: H2 = relu(H1 W1^T + b1)
     {
       float av[2][NGP_HID / 4];
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s) {
-        av[0][s] = H1[li * FB_SH + 4 * s + kq];
-        av[1][s] = H1[(16 + li) * FB_SH + 4 * s + kq];
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) { h2r[0][nt] = f32x4{bb1[nt], bb1[nt], bb1[nt], bb1[nt]}; h2r[1][nt] = h2r[0][nt]; }
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
+      fp_row_frags(H1, FB_SH, li, kq, av);
+      fp_row_fill(h2r, bb1);
 #if FP_W1_REGS >= 1
-          const float b = bw1[s][nt];
+      fp_row_gemm(av, [&](int s, int nt) { return bw1[s][nt]; }, h2r);
 #else
-          const float b = W[FB_W1 + (nt * 16 + li) * FB_SH + 4 * s + kq];
+      fp_row_gemm(av, [&](int s, int nt) { return W[FB_W1 + (nt * 16 + li) * FB_SH + 4 * s + kq]; }, h2r);
 #endif
-          h2r[0][nt] = sf_mfma4(av[0][s], b, h2r[0][nt]);
-          h2r[1][nt] = sf_mfma4(av[1][s], b, h2r[1][nt]);
-        }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            h2r[mt][nt][r] = fmaxf(h2r[mt][nt][r], 0.0f);
-            H2[(mt * 16 + 4 * kq + r) * FB_SH + nt * 16 + li] = h2r[mt][nt][r];
-          }
+      fp_row_store<4>(H2, FB_SH, li, kq, [&](int mt, int nt, int r) { return h2r[mt][nt][r] = fmaxf(h2r[mt][nt][r], 0.0f); });
     }
     sf_wave_sync();
     // ---- C: out = H2 W2^T + b2 on the matrix cores (lanes li < 4 hold out[point][o = li]), through DO to lane = (point pl, half),
     // which owns outputs 2*half, 2*half + 1 and turns them into d(out)
     {
       float av[2][NGP_HID / 4];
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s) {
-        av[0][s] = H2[li * FB_SH + 4 * s + kq];
-        av[1][s] = H2[(16 + li) * FB_SH + 4 * s + kq];
-      }
-      f32x4 c[2];
-      c[0] = f32x4{cb2, cb2, cb2, cb2};
-      c[1] = c[0];
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s) {
-        c[0] = sf_mfma4(av[0][s], cw2[s], c[0]);
-        c[1] = sf_mfma4(av[1][s], cw2[s], c[1]);
-      }
-      if (li < NGP_OUT) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) DO[(mt * 16 + 4 * kq + r) * 4 + li] = c[mt][r];
-      }
+      fp_row_frags(H2, FB_SH, li, kq, av);
+      f32x4 c[2][1];
+      fp_row_fill(c, cb2);
+      fp_row_gemm(av, [&](int s, int) { return cw2[s]; }, c);
+      if (li < NGP_OUT) fp_row_store<1>(DO, 4, li, kq, [&](int mt, int, int r) { return c[mt][0][r]; });
       sf_wave_sync();
       const float o0 = DO[pl * 4 + 2 * half], o1 = DO[pl * 4 + 2 * half + 1];
       float d0 = 0.0f, d1 = 0.0f;
@@ -271,34 +332,25 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
     // ---- D: dW2[o][k] += sum_p dout[p][o] h2[p][k] (A = dout^T, rows o >= 4 zero; B = h2; K = the 32 points, ascending);  db2
     // ---- E: dh2 = (dout W2) masked by h2 > 0, over h2
     {
-      float da[FB_PTS / 4], hb[FB_PTS / 4][4], ea[2];
+      float da[FB_PTS / 4][1], hb[FB_PTS / 4][4], one[FB_PTS / 4][1], ea[2][1];
 #pragma unroll
       for (int s = 0; s < FB_PTS / 4; ++s) {
         const float v = DO[(4 * s + kq) * 4 + (li & 3)];
-        da[s] = li < NGP_OUT ? v : 0.0f;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) hb[s][kt] = H2[(4 * s + kq) * FB_SH + kt * 16 + li];
+        da[s][0] = li < NGP_OUT ? v : 0.0f;
+        one[s][0] = 1.0f;
       }
-      ea[0] = DO[li * 4 + kq];
-      ea[1] = DO[(16 + li) * 4 + kq];
-      f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
+      fp_point_frags(H2, FB_SH, li, kq, hb);
+      fp_row_frags(DO, 4, li, kq, ea);
+      f32x4 b[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
+      fp_points_gemm(da, hb, acc2);
+      fp_points_gemm(da, one, b);
 #pragma unroll
-      for (int s = 0; s < FB_PTS / 4; ++s) {
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) acc2[kt] = sf_mfma4(da[s], hb[s][kt], acc2[kt]);
-        b = sf_mfma4(da[s], 1.0f, b);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) accb2[r] += b[r];
+      for (int r = 0; r < 4; ++r) accb2[r] += b[0][0][r];
       sf_wave_sync();                                    // every lane holds its h2 fragments: dh2 goes over h2
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const f32x4 g = sf_mfma4(ea[mt], ew2[nt], f32x4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-          for (int r = 0; r < 4; ++r) H2[(mt * 16 + 4 * kq + r) * FB_SH + nt * 16 + li] = h2r[mt][nt][r] > 0.0f ? g[r] : 0.0f;
-        }
+      f32x4 g[2][4];
+      fp_row_fill(g, zero4);
+      fp_row_gemm(ea, [&](int, int nt) { return ew2[nt]; }, g);
+      fp_row_store<4>(H2, FB_SH, li, kq, [&](int mt, int nt, int r) { return h2r[mt][nt][r] > 0.0f ? g[mt][nt][r] : 0.0f; });
     }
     sf_wave_sync();
     // ---- F: dW1[j][k] += sum_p dh2[p][j] h1[p][k]   (A = dh2^T, B = h1; K = the 32 points);  db1[j = lane], points ascending
@@ -307,21 +359,11 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
 #pragma unroll
       for (int hs = 0; hs < 2; ++hs) {                   // 16 points at a time: 80 fragment registers instead of 160
         float av[FB_PTS / 8][4], bv[FB_PTS / 8][4], col[FB_PTS / 2];
-#pragma unroll
-        for (int s = 0; s < FB_PTS / 8; ++s)
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            av[s][t] = H2[(16 * hs + 4 * s + kq) * FB_SH + t * 16 + li];
-            bv[s][t] = H1[(16 * hs + 4 * s + kq) * FB_SH + t * 16 + li];
-          }
+        fp_point_frags(H2 + 16 * hs * FB_SH, FB_SH, li, kq, av);
+        fp_point_frags(H1 + 16 * hs * FB_SH, FB_SH, li, kq, bv);
 #pragma unroll
         for (int q = 0; q < FB_PTS / 2; ++q) col[q] = H2[(16 * hs + q) * FB_SH + lane];
-#pragma unroll
-        for (int s = 0; s < FB_PTS / 8; ++s)
-#pragma unroll
-          for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) acc1[jt][kt] = sf_mfma4(av[s][jt], bv[s][kt], acc1[jt][kt]);
+        fp_points_gemm(av, bv, acc1);
 #pragma unroll
         for (int q = 0; q < FB_PTS / 2; ++q) b += col[q];
       }
@@ -330,61 +372,30 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
     // ---- G: dh1 = (dh2 W1) masked by h1 > 0, written over h1 (phase F holds its h1 fragments: wave barrier before the stores)
     {
       float av[2][NGP_HID / 4];
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s) {
-        av[0][s] = H2[li * FB_SH + 4 * s + kq];
-        av[1][s] = H2[(16 + li) * FB_SH + 4 * s + kq];
-      }
+      fp_row_frags(H2, FB_SH, li, kq, av);
       f32x4 c[2][4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) { c[0][nt] = f32x4{0.f, 0.f, 0.f, 0.f}; c[1][nt] = c[0][nt]; }
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
+      fp_row_fill(c, zero4);
 #if FP_W1_REGS >= 2
-          const float b = gw1[s][nt];
+      fp_row_gemm(av, [&](int s, int nt) { return gw1[s][nt]; }, c);
 #else
-          const float b = W[FB_W1 + (4 * s + kq) * FB_SH + nt * 16 + li];
+      fp_row_gemm(av, [&](int s, int nt) { return W[FB_W1 + (4 * s + kq) * FB_SH + nt * 16 + li]; }, c);
 #endif
-          c[0][nt] = sf_mfma4(av[0][s], b, c[0][nt]);
-          c[1][nt] = sf_mfma4(av[1][s], b, c[1][nt]);
-        }
       sf_wave_sync();
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float* hp = H1 + (mt * 16 + 4 * kq + r) * FB_SH + nt * 16 + li;
 #if FP_H1_REGS
-            *hp = h1r[mt][nt][r] > 0.0f ? c[mt][nt][r] : 0.0f;
+      fp_row_store<4>(H1, FB_SH, li, kq, [&](int mt, int nt, int r) { return h1r[mt][nt][r] > 0.0f ? c[mt][nt][r] : 0.0f; });
 #else
-            *hp = *hp > 0.0f ? c[mt][nt][r] : 0.0f;
+      fp_row_store<4>(H1, FB_SH, li, kq, [&](int mt, int nt, int r) { return H1[fp_row_at(FB_SH, li, kq, mt, nt, r)] > 0.0f ? c[mt][nt][r] : 0.0f; });
 #endif
-          }
     }
     sf_wave_sync();
     // ---- H: dW0[j][f] += sum_p dh1[p][j] feat[p][f];  db0[j = lane], points ascending
     {
       float av[FB_PTS / 4][4], bv[FB_PTS / 4][2], col[FB_PTS];
-#pragma unroll
-      for (int s = 0; s < FB_PTS / 4; ++s) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) av[s][t] = H1[(4 * s + kq) * FB_SH + t * 16 + li];
-        bv[s][0] = F[(4 * s + kq) * FB_SF + li];
-        bv[s][1] = F[(4 * s + kq) * FB_SF + 16 + li];
-      }
+      fp_point_frags(H1, FB_SH, li, kq, av);
+      fp_point_frags(F, FB_SF, li, kq, bv);
 #pragma unroll
       for (int q = 0; q < FB_PTS; ++q) col[q] = H1[q * FB_SH + lane];
-#pragma unroll
-      for (int s = 0; s < FB_PTS / 4; ++s)
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) {
-          acc0[jt][0] = sf_mfma4(av[s][jt], bv[s][0], acc0[jt][0]);
-          acc0[jt][1] = sf_mfma4(av[s][jt], bv[s][1], acc0[jt][1]);
-        }
+      fp_points_gemm(av, bv, acc0);
       float b = 0.0f;
 #pragma unroll
       for (int q = 0; q < FB_PTS; ++q) b += col[q];
@@ -393,53 +404,15 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
     // ---- I: d(feat) = dh1 W0 -> level-major [L][P][2] (zero for points outside the grid)
     if (a.dfeat_out) {
       float av[2][NGP_HID / 4], bv[NGP_HID / 4][2];
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s) {
-        av[0][s] = H1[li * FB_SH + 4 * s + kq];
-        av[1][s] = H1[(16 + li) * FB_SH + 4 * s + kq];
-        bv[s][0] = W[FB_W0 + (4 * s + kq) * FB_SF + li];
-        bv[s][1] = W[FB_W0 + (4 * s + kq) * FB_SF + 16 + li];
-      }
+      fp_row_frags(H1, FB_SH, li, kq, av);
+      fp_point_frags(W + FB_W0, FB_SF, li, kq, bv);
       f32x4 c[2][2];
-      c[0][0] = c[0][1] = c[1][0] = c[1][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < NGP_HID / 4; ++s) {
-        c[0][0] = sf_mfma4(av[0][s], bv[s][0], c[0][0]);
-        c[0][1] = sf_mfma4(av[0][s], bv[s][1], c[0][1]);
-        c[1][0] = sf_mfma4(av[1][s], bv[s][0], c[1][0]);
-        c[1][1] = sf_mfma4(av[1][s], bv[s][1], c[1][1]);
-      }
-      // through the (now free) F tile, as k_ngp_field_bwd_mfma: lane = (level lane >> 2, quarter lane & 3) owns 8 consecutive
-      // points of one level = 64 contiguous bytes of the level-major [L][P][2] image
+      fp_row_fill(c, zero4);
+      fp_row_gemm(av, [&](int s, int ft) { return bv[s][ft]; }, c);
       sf_wave_sync();                                    // phase H holds its F fragments
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int q = mt * 16 + 4 * kq + r, f = ft * 16 + li;
-            F[q * FB_SF + f] = INS[q] != 0.0f ? c[mt][ft][r] : 0.0f;
-          }
+      fp_row_store<2>(F, FB_SF, li, kq, [&](int mt, int ft, int r) { return INS[mt * 16 + 4 * kq + r] != 0.0f ? c[mt][ft][r] : 0.0f; });
       sf_wave_sync();
-      {
-        const uint32_t l = lane >> 2, q0 = (lane & 3) * 8;
-        if (l < a.lv.L) {
-          float* dst = a.dfeat_out + ((size_t)l * a.dfeat_P + a.p_off + p0 + q0) * 2;
-          if (p0 + FB_PTS <= a.P && !((a.dfeat_P | a.p_off) & 1)) {      // whole trip, 16-byte aligned rows
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              f32x4 v;
-              v[0] = F[(q0 + 2 * j) * FB_SF + 2 * l];     v[1] = F[(q0 + 2 * j) * FB_SF + 2 * l + 1];
-              v[2] = F[(q0 + 2 * j + 1) * FB_SF + 2 * l]; v[3] = F[(q0 + 2 * j + 1) * FB_SF + 2 * l + 1];
-              *reinterpret_cast<f32x4*>(dst + 4 * j) = v;
-            }
-          } else {                                         // ragged last trip (or an odd point count)
-            for (int j = 0; j < 8; ++j)
-              if (p0 + q0 + j < a.P) { dst[2 * j] = F[(q0 + j) * FB_SF + 2 * l]; dst[2 * j + 1] = F[(q0 + j) * FB_SF + 2 * l + 1]; }
-          }
-        }
-      }
+      fp_store_dfeat(a, F, p0, lane);
     }
     sf_wave_sync();                                      // before the next trip restages F / H1 / H2 / DO / INS
 #if FP_PREFETCH
@@ -449,27 +422,5 @@ SF_KERNEL(256) void k_ngp_field_bwd_pipe(FBArgs a) {
   }
 #undef FP_POINT
 
-  // ---- flush this wave's gradient tiles as fixed-point integer adds: the same addends as k_ngp_field_bwd_mfma's waves
-#pragma unroll
-  for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = jt * 16 + 4 * kq + r;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) sf_grad_add(a.g_w1 + j * NGP_HID + kt * 16 + li, a.f_w1 + j * NGP_HID + kt * 16 + li, acc1[jt][kt][r], a.thr);
-      sf_grad_add(a.g_w0 + j * NGP_FEAT + li, a.f_w0 + j * NGP_FEAT + li, acc0[jt][0][r], a.thr);
-      sf_grad_add(a.g_w0 + j * NGP_FEAT + 16 + li, a.f_w0 + j * NGP_FEAT + 16 + li, acc0[jt][1][r], a.thr);
-    }
-  if (kq == 0) {
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sf_grad_add(a.g_w2 + r * NGP_HID + kt * 16 + li, a.f_w2 + r * NGP_HID + kt * 16 + li, acc2[kt][r], a.thr);
-    if (li == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sf_grad_add(a.g_b2 + r, a.f_b2 + r, accb2[r], a.thr);
-    }
-  }
-  sf_grad_add(a.g_b1 + lane, a.f_b1 + lane, accb1, a.thr);
-  sf_grad_add(a.g_b0 + lane, a.f_b0 + lane, accb0, a.thr);
+  fp_flush(a, lane, acc1, acc0, acc2, accb2, accb1, accb0);
 }

@@ -13,13 +13,15 @@
 //   * backward RECOMPUTES the field forward instead of saving activations (VALU is cheap, HBM is
 //     not); MLP weight gradients are formed per 256-point tile as LDS-staged outer-product
 //     sums, one atomic flush per workgroup; table gradients use fp32 L2 atomics.
-// Per-thread math lives in ngp_device.h (also compiled for the host by tests/hostemu).
+// Per-thread math lives in ngp_device.h, the backward's host plan (chunks, launch geometry, level split, workspace sizes) in
+// ngp_bwd_plan.h (both also compiled for the host by tests/hostemu).
 //
 // Layouts (row-major): z_c,sig_c [N,T]; rgb_c [N,T,3]; z_f,sig_f,rgb_f same; z_sorted,sigma_s
 // [N,2T]; rgb_s [N,2T,3]; image [N,3]; depth, weights_sum, nears, fars [N].
 
 #include "sf_common.h"
 #include "ngp_device.h"
+#include "ngp_bwd_plan.h"
 #include "ngp_field_lds.h"
 #include "ngp_bwd_mfma.h"
 #include "ngp_bwd_pipe.h"
@@ -115,6 +117,9 @@ __global__ __launch_bounds__(64) void k_ngp_sample_fine(
 #define SC_RAYS 64
 #define SC_SLOTS 4096
 #define SC_EMPTY 0xffffffffu
+#ifndef SC_RUN
+#define SC_RUN 32u              // sorted samples merged per thread before the cache (`sc_run` below; measured with the level split, ngp_bwd_plan.h)
+#endif
 // NT threads share one 80 KB LDS cache (4096 slots of 64-bit fixed-point sums; r02: 8192 of floats) (one workgroup per CU): NT = 1024 puts 4 waves on every SIMD -- the loop body is a
 // chain of dependent global loads, hash arithmetic and LDS atomics, and with the first version's 256 threads (ONE wave per
 // SIMD) every one of those latencies was exposed.  `last_level`: levels [0, last_level) are walked by this kernel.
@@ -323,55 +328,10 @@ extern "C" int sf_ngp_density(const sf_ngp_field* f, const float* xyz, uint32_t 
   return SF_OK;
 }
 
-// workspace (floats): forward z_c, sig_c [N*T]; rgb_c [3NT]; z_f, sig_f [N*T]; rgb_f [3NT]  -> 10*N*T
-// backward: dsig [2NT] + drgb [6NT] + d(features) level-major [16][2NT][2] = 72*N*T, then the binned scatter's cursors and entries.
-// the backward cuts the rays into chunks (pipeline below): as many as keep a chunk a multiple of 256 rays and >= 2048 rays
-#ifndef NGP_BWD_CHUNKS
-#define NGP_BWD_CHUNKS 2u       // r03 (atomic scatters): 1 / 2 / 4 / 8 chunks = 5.96 / 5.65 / 5.64 / 6.00 ms; r04 (binned): 1 / 2 / 4 / 8 = 3.71 / 3.55 / 3.68 / 4.11 ms
-#endif
-struct NgpChunks { uint32_t n, max_rays, start[66]; };      // chunk c = rays [start[c], start[c + 1])
-static NgpChunks ngp_bwd_plan(uint32_t N) {
-  NgpChunks c{};
-  auto equal = [&](uint32_t k) {
-    c.n = k; c.max_rays = N / k;
-    for (uint32_t i = 0; i <= k; ++i) c.start[i] = i * (N / k);
-  };
-  auto ok = [&](uint32_t rays, uint32_t k) { return k >= 1 && rays % k == 0 && (rays / k) % 256 == 0 && rays / k >= 2048; };
-  // (a small first chunk, so that the side stream starts early, measured slower: first chunk 1/4, 1/8, 1/16 of the rays = 3.63 / 3.63 /
-  // 3.66 ms against 3.54 for two equal chunks, profiles/r04_ngp_binned_tuning.log -- co-running kernels cost their sum, not their maximum)
-  // large ray sets: chunks of at most 8192 rays, so that the bins of one chunk (the workspace) stay at 1.6 GB
-  for (uint32_t k = (N + 8191) / 8192; k > NGP_BWD_CHUNKS && k <= 64; ++k)
-    if (ok(N, k)) { equal(k); return c; }
-  uint32_t k = NGP_BWD_CHUNKS;
-  while (k > 1 && !ok(N, k)) --k;
-  if (N / k > 8192) {                   // (r06, ADVICE r05: also when an equal split exists but is coarser than 8192 rays -- N = 51 712 = 2 x 25 856)
-    // r05: a ray count with no equal split (N = 200^2, 65 535, ...) used to fall back to ONE chunk, and the bins -- sized by
-    // the largest chunk -- then grew with all rays (7.9 GB at 40 000 rays, 13 GB at 65 535).  Unequal chunks: as many chunks of `per`
-    // rays (a multiple of 256, 8192 unless that needs more than 64 chunks) as fit, and the remainder as the last one; the kernels take
-    // any (offset, count) -- only the bins' size depends on max_rays.
-    uint32_t per = 8192;
-    if ((N + per - 1) / per > 64) per = (((N + 63) / 64 + 255) / 256) * 256;
-    c.n = (N + per - 1) / per; c.max_rays = per;
-    for (uint32_t i = 0; i < c.n; ++i) c.start[i] = i * per;
-    c.start[c.n] = N;
-    return c;
-  }
-  equal(k);
-  return c;
-}
-// binned scatter (ngp_scatter_bin.h): cursors + 16-byte entries of ONE chunk: 4 corner pairs x every level + slack per bucket
-#define SB_CURSOR_WORDS (NGP_MAX_LEVELS * SB_MAX_BUCKETS)
-#ifndef SB_LEVELS_BUDGET
-#define SB_LEVELS_BUDGET 24                       // entries for 24 level-slots per sample (12 levels are binned): a bucket holds 2 x its uniform
-#endif                                            // share (max / mean of the bucket loads on the reference scene: <= 1.9; 16 / 24 / 32 slots: 3.61 / 3.55 / 3.58 ms)
-static uint64_t ngp_bin_entries(uint32_t N, uint32_t T) {
-  return (uint64_t)ngp_bwd_plan(N).max_rays * 2 * T * 4 * SB_LEVELS_BUDGET + (uint64_t)SB_CURSOR_WORDS * 64;
-}
-extern "C" uint64_t sf_ngp_render_workspace_bytes(uint32_t N, uint32_t T) {
-  return (uint64_t)(8 + 4 * NGP_MAX_LEVELS) * N * T * sizeof(float) + (uint64_t)SB_CURSOR_WORDS * 4 + ngp_bin_entries(N, T) * 16;
-}
+// workspace sizes: the formulas and the layouts behind them are in ngp_bwd_plan.h
+extern "C" uint64_t sf_ngp_render_workspace_bytes(uint32_t N, uint32_t T) { return ngp_render_workspace_bytes(N, T); }
 
-extern "C" uint64_t sf_ngp_render_forward_workspace_bytes(uint32_t N, uint32_t T) { return (uint64_t)10 * N * T * sizeof(float); }
+extern "C" uint64_t sf_ngp_render_forward_workspace_bytes(uint32_t N, uint32_t T) { return ngp_render_forward_workspace_bytes(N, T); }
 
 // Grid of k_ngp_field_mfma: 256 CUs x the two 256-thread workgroups its registers leave room for, every workgroup resident from the
 // start (a workgroup stages the weights once).  Render forward at 128 x 128 rays, 512 / 1024 / 2048 workgroups: 0.89 / 0.91 / 0.93 ms;
@@ -513,6 +473,94 @@ extern "C" int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* 
   return SF_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// backward: what the library keeps per device, and the two guards of a call
+// ---------------------------------------------------------------------------
+static constexpr size_t FB_LDS_BYTES = (size_t)FB_LDS_FLOATS * sizeof(float);
+static constexpr size_t SC_LDS_BYTES = (size_t)SC_SLOTS * (sizeof(uint32_t) + 2 * sizeof(long long));
+
+static int ngp_bwd_raise_lds_limits() {             // raised dynamic-LDS limits are per-device function attributes
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess)
+    SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot raise the dynamic LDS limits");
+  return SF_OK;
+}
+
+// One per device (the first 32), filled on first use under g_bwd_dev_mu and kept for the life of the process.
+struct NgpBwdDevice {
+  // the gradient accumulators come from a memory pool this library owns (kept mapped between calls so a call does not re-map it); the
+  // device's default pool and its settings are left alone
+  hipMemPool_t pool;
+  // The side stream and its fork / join events are ONE set per device: two host threads (or two caller streams) rendering on the
+  // same device would re-record each other's events, so the whole fork .. join section of a call runs under g_bwd_side_mu (host-side
+  // enqueue only: microseconds).
+  hipStream_t side; hipEvent_t fork, join;
+  bool lds_raised;
+};
+static std::mutex g_bwd_dev_mu, g_bwd_side_mu;
+static NgpBwdDevice g_bwd_dev[32] = {};
+
+// The state of device dev_id with the LDS limits raised, and with a side stream if the call wants one.  Devices beyond the 32nd keep no
+// state (*out = nullptr: hipMallocAsync, no side stream) and have their limits raised by every call.
+static int ngp_bwd_device(int dev_id, bool want_side, NgpBwdDevice** out) {
+  *out = nullptr;
+  if (dev_id >= 32) return ngp_bwd_raise_lds_limits();
+  std::lock_guard<std::mutex> lk(g_bwd_dev_mu);
+  NgpBwdDevice& d = g_bwd_dev[dev_id];
+  if (!d.pool) {
+    hipMemPoolProps props{};
+    props.allocType = hipMemAllocationTypePinned;
+    props.location.type = hipMemLocationTypeDevice;
+    props.location.id = dev_id;
+    hipMemPool_t np = nullptr;
+    uint64_t keep = UINT64_MAX;
+    if (hipMemPoolCreate(&np, &props) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot create the scratch pool");
+    if (hipMemPoolSetAttribute(np, hipMemPoolAttrReleaseThreshold, &keep) != hipSuccess) {
+      (void)hipMemPoolDestroy(np);
+      SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot configure the scratch pool");
+    }
+    d.pool = np;
+  }
+  if (!d.lds_raised) {
+    if (int rc = ngp_bwd_raise_lds_limits()) return rc;
+    d.lds_raised = true;
+  }
+  if (want_side && !d.side) {
+    hipStream_t s = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess) {
+      if (fork) (void)hipEventDestroy(fork);
+      if (s) (void)hipStreamDestroy(s);
+      SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot create the side stream");
+    }
+    d.fork = fork; d.join = join; d.side = s;
+  }
+  *out = &d;
+  return SF_OK;
+}
+
+// the gradient accumulators of one call: freed on the stream, behind everything the call enqueued
+struct FixBuf {
+  long long* p = nullptr; hipStream_t st = nullptr;
+  ~FixBuf() { if (p) (void)hipFreeAsync(p, st); }
+};
+
+// Joins the side stream into the caller's stream on EVERY exit path of a call that forked, error returns included.
+struct SideJoin {
+  NgpBwdDevice* dev = nullptr; hipStream_t st = nullptr; bool forked = false;
+  int fork() {                                     // the side stream continues from here
+    if (hipEventRecord(dev->fork, st) != hipSuccess || hipStreamWaitEvent(dev->side, dev->fork, 0) != hipSuccess) return 1;
+    forked = true;
+    return 0;
+  }
+  int join() { const bool f = forked; forked = false; return (!f || (hipEventRecord(dev->join, dev->side) == hipSuccess && hipStreamWaitEvent(st, dev->join, 0) == hipSuccess)) ? 0 : 1; }
+  ~SideJoin() { (void)join(); }
+};
+
 extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_grad* g, const float* rays_o,
                                       const float* rays_d, const float* aabb, uint32_t N, uint32_t T,
                                       const float* nears, const float* fars, const float* z_sorted,
@@ -527,15 +575,31 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   NgpLevels lv;
   if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
   const uint64_t M = (uint64_t)N * 2 * T;
+  const uint32_t T2 = 2 * T;
   float* dsig = workspace;
   float* drgb = dsig + M;
+  float* dfeat = g->g_embeddings ? drgb + 3 * M : nullptr;        // NULL table gradient = table frozen
+  uint32_t* bin_cursor = reinterpret_cast<uint32_t*>(workspace + ngp_bwd_grad_floats(N, T));
+  f32x4* bin_ent = reinterpret_cast<f32x4*>(bin_cursor + SB_CURSOR_WORDS);      // (16-byte aligned: 72 N T floats + 2^13 words)
+  // the plan (ngp_bwd_plan.h): which kernel scatters which level, and the ray chunks (the entries buffer is sized for this chunking)
+  const NgpScatterPlan sp = ngp_scatter_plan(lv, dfeat != nullptr, N, T);
+  const bool per_chunk = dfeat && sp.last < lv.L;                 // levels [last, L) are scattered chunk by chunk
+  const NgpChunks plan = per_chunk ? ngp_bwd_plan(N) : ngp_bwd_one_chunk(N);
+  const float thr_mlp = ngp_bwd_thr_mlp(plan.n);
+  // a fixed-point sum receives at most 8 addends per sample (the 8 corners of a cell, hash collisions included): thresholds per
+  // sf_dev.h keep every table sum below 2^18; larger addends take the fp32 atomics (sf_grad_add)
+  const float thr_tab = sf_fix_thr(8.0 * (double)M);
+
   // wave-per-ray backward: the forward's scans run in reverse (suffix sums in double)
   k_ngp_composite_bwd_wave<<<sf_div_up(N, 4), 256, 0, st>>>(
       CompositeBwdArgs{z_sorted, sigma_s, rgb_s, nears, fars, N, T, bg_color, grad_image, grad_weights_sum, dsig, drgb});
   SF_CHECK_LAUNCH("ngp_composite_bwd");
-  int dev_id = 0;                                  // raised dynamic-LDS limits are per-device function attributes
+
+  int dev_id = 0;
   if (hipGetDevice(&dev_id) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "hipGetDevice failed");
-  float* dfeat = g->g_embeddings ? drgb + 3 * M : nullptr;        // NULL table gradient = table frozen
+  NgpBwdDevice* dev = nullptr;
+  if (int rc = ngp_bwd_device(dev_id, per_chunk, &dev)) return rc;
+
   // every gradient is first summed in 64-bit fixed point (sf_dev.h: order-independent, so the result is the same on every run) in a
   // stream-ordered scratch buffer: [table rows x 2 | w0 | b0 | w1 | b1 | w2 | b2], converted into the caller's buffers at the end
   const uint64_t tab_n = dfeat ? (uint64_t)f->h_offsets[f->L] * 2 : 0;
@@ -546,97 +610,34 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
     uint64_t e = 0;
     for (int k = 0; k < FIX_SEGS; ++k) { segs.dst[k] = dst[k]; e += len[k]; segs.end[k] = e; }
   }
-  // the scratch comes from a memory pool this library owns (one per device, created once under a lock, kept mapped between calls so
-  // a call does not re-map it); the device's default pool and its settings are left alone
-  static std::mutex pool_mu;
-  static hipMemPool_t pools[32] = {};
-  hipMemPool_t pool = nullptr;
-  if (dev_id < 32) {
-    std::lock_guard<std::mutex> lk(pool_mu);
-    if (!pools[dev_id]) {
-      hipMemPoolProps props{};
-      props.allocType = hipMemAllocationTypePinned;
-      props.location.type = hipMemLocationTypeDevice;
-      props.location.id = dev_id;
-      hipMemPool_t np = nullptr;
-      uint64_t keep = UINT64_MAX;
-      if (hipMemPoolCreate(&np, &props) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot create the scratch pool");
-      if (hipMemPoolSetAttribute(np, hipMemPoolAttrReleaseThreshold, &keep) != hipSuccess) {
-        (void)hipMemPoolDestroy(np);
-        SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot configure the scratch pool");
-      }
-      pools[dev_id] = np;
-    }
-    pool = pools[dev_id];
-  }
-  struct FixBuf {
-    long long* p = nullptr; hipStream_t st = nullptr;
-    ~FixBuf() { if (p) (void)hipFreeAsync(p, st); }
-  } fix;
+  FixBuf fix;
   fix.st = st;
   const uint64_t fix_bytes = segs.end[FIX_SEGS - 1] * sizeof(long long);
-  const hipError_t alloc = pool ? hipMallocFromPoolAsync(reinterpret_cast<void**>(&fix.p), fix_bytes, pool, st)
+  const hipError_t alloc = dev ? hipMallocFromPoolAsync(reinterpret_cast<void**>(&fix.p), fix_bytes, dev->pool, st)
                                : hipMallocAsync(reinterpret_cast<void**>(&fix.p), fix_bytes, st);
   if (alloc != hipSuccess || !fix.p)
     SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot allocate the gradient accumulators");
   if (hipMemsetAsync(fix.p, 0, fix_bytes, st) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: memset failed");
   long long* acc_tab = fix.p;
-  long long* acc_mlp = fix.p + tab_n;
-  // a fixed-point sum receives at most 8 addends per sample (the 8 corners of a cell, hash collisions included): thresholds per
-  // sf_dev.h keep every table sum below 2^18; larger addends take the fp32 atomics (sf_grad_add)
-  const float thr_tab = sf_fix_thr(8.0 * (double)M);
-  const size_t lds2 = (size_t)FB_LDS_FLOATS * sizeof(float);
-  const size_t lds_sc = (size_t)SC_SLOTS * (sizeof(uint32_t) + 2 * sizeof(long long));
-  static unsigned attr_mask = 0;
-  if (dev_id >= 32 || !(attr_mask & (1u << dev_id))) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc) != hipSuccess)
-      SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot raise the dynamic LDS limits");
-    if (dev_id < 32) attr_mask |= 1u << dev_id;
-  }
-  // scatter shape, measured on MI355X in r02 (the A/B environment switches were retired in r04): 1024 threads per cached-level
-  // workgroup (256 / 512 / 1024: 8.55 / - / 7.84 ms render fwd+bwd), LDS cache up to scale 640 (160 / 320 / 640 / all levels: 7.82 /
-  // 7.63 / 7.51 / 8.27 ms), the finer levels in their own high-occupancy launch, 32 sorted samples merged per thread before the cache
-  // (4 / 8 / 16 / 32: 6.95 / 6.85 / 6.81 / 6.76 ms)
-  constexpr float sc_cutoff = 640.0f;
-#ifndef SC_RUN
-#define SC_RUN 32u
-#endif
-  constexpr uint32_t sc_run = SC_RUN;
-  // levels up to scale ~640 profit from the LDS cache (measured r02: cut-off 160 / 320 / 640 / none = 7.82 / 7.63 / 7.51 / 8.27 ms render fwd+bwd)
-  uint32_t cached = 0;
-  while (cached < lv.L && lv.scale[cached] <= sc_cutoff) ++cached;
-  // r04: the levels whose cell is smaller than a ray patch's footprint (no merging in the LDS cache) are BINNED by table slice and
-  // reduced in LDS instead of sending one device atomic per corner (ngp_scatter_bin.h); tables beyond 2^22 rows keep the atomics
-  // (measured r04, render fwd + bwd: atomics 5.02 ms; binned from scale > 45 / 60 / 80 / 112 / 160: 4.97 / 4.45 / 4.50 / 4.43 / 4.58 ms with
-  // one entry per corner, 60 / 112: 4.20 / 4.21 ms with pair entries, profiles/r04_ngp_binned_scatter_ab.log; the A/B switches are
-  // retired: the dense levels keep the LDS cache, the hashed ones are binned)
-  constexpr float bin_cutoff = 60.0f;
-  uint32_t first_bin = lv.L;
-  uint32_t bucket0[NGP_MAX_LEVELS + 1] = {};
-  if (dfeat) {
-    first_bin = 0;
-    while (first_bin < lv.L && lv.scale[first_bin] <= bin_cutoff) ++first_bin;
-    uint32_t tb = 0;
-    for (uint32_t l = 0; l <= NGP_MAX_LEVELS; ++l) {
-      bucket0[l] = tb;
-      if (l >= first_bin && l < lv.L) {
-        const uint32_t nb = (lv.hsize[l] + SB_ROWS - 1) >> SB_ROWS_LOG;
-        if (nb > SB_MAX_BUCKETS) { first_bin = lv.L; break; }
-        tb += nb;
-      }
-    }
-  }
-  const bool binned = first_bin < lv.L;
-  if (binned && cached > first_bin) cached = first_bin;
-  const uint32_t last = !dfeat ? lv.L : binned ? first_bin : cached;     // levels [0, last): k_ngp_scatter, [last, L): binned / k_ngp_scatter_fine
-  const uint32_t total_buckets = bucket0[NGP_MAX_LEVELS];
-  uint32_t* bin_cursor = reinterpret_cast<uint32_t*>(workspace + (size_t)(8 + 4 * NGP_MAX_LEVELS) * N * T);
-  f32x4* bin_ent = reinterpret_cast<f32x4*>(bin_cursor + SB_CURSOR_WORDS);      // (16-byte aligned: 72 N T floats + 2^13 words)
-  const uint64_t bin_entries = ngp_bin_entries(N, T);
-  const uint32_t bin_cap = binned ? (uint32_t)(bin_entries / total_buckets) : 0;
-  if (binned && hipMemsetAsync(bin_cursor, 0, (size_t)total_buckets * 4, st) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: memset failed");
+  if (sp.binned && hipMemsetAsync(bin_cursor, 0, (size_t)sp.total_buckets * 4, st) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: memset failed");
+
+  // what every chunk's launches share
+  FBArgs a{};
+  a.table = f->embeddings; a.w0 = f->w0; a.b0 = f->b0; a.w1 = f->w1; a.b1 = f->b1; a.w2 = f->w2; a.b2 = f->b2; a.bound = f->bound;
+  a.g_w0 = fix.p + segs.end[0]; a.g_b0 = fix.p + segs.end[1]; a.g_w1 = fix.p + segs.end[2];
+  a.g_b1 = fix.p + segs.end[3]; a.g_w2 = fix.p + segs.end[4]; a.g_b2 = fix.p + segs.end[5];
+  a.f_w0 = g->g_w0; a.f_b0 = g->g_b0; a.f_w1 = g->g_w1; a.f_b1 = g->g_b1; a.f_w2 = g->g_w2; a.f_b2 = g->g_b2; a.thr = thr_mlp;
+  a.lv = lv; a.aabb = aabb; a.dfeat_out = dfeat; a.T2 = T2; a.dfeat_P = (uint32_t)M;
+  a.feat_c = field_cache;                           // (or all three null: the kernel re-gathers the features)
+  a.feat_f = field_cache ? field_cache + (size_t)N * T * NGP_FEAT : nullptr;
+  a.perm = field_cache ? reinterpret_cast<const uint32_t*>(field_cache + 2 * (size_t)N * T * NGP_FEAT) : nullptr;
+  SBArgs b{};
+  b.lv = lv; b.bound = f->bound; b.aabb = aabb; b.dfeat = dfeat;
+  b.gtable = acc_tab; b.gtable_f = g->g_embeddings; b.thr = thr_tab; b.cursor = bin_cursor; b.ent = bin_ent;
+  b.T2 = T2; b.first_level = sp.first_bin; b.P_stride = (uint32_t)M; b.cap = sp.bin_cap;
+  SBRArgs r{};
+  r.lv = lv; r.gtable = acc_tab; r.gtable_f = g->g_embeddings; r.thr = thr_tab; r.cursor = bin_cursor; r.ent = bin_ent; r.first_level = sp.first_bin; r.cap = sp.bin_cap;
+  for (uint32_t l = 0; l <= NGP_MAX_LEVELS; ++l) { b.bucket0[l] = sp.bucket0[l]; r.bucket0[l] = sp.bucket0[l]; }
 
   // ---- the pipeline (r03).  Three kernels with three different bottlenecks: the field backward (fp32 MFMA + 113 KB of LDS,
   // one workgroup per CU), the fine-level scatter (memory-side atomic unit, no LDS, VALU idle) and the cached-level scatter
@@ -644,91 +645,48 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   // field backward of chunk c + 1 occupies the CUs, and the last one runs beside the cached-level scatter (one launch over
   // all rays, its LDS cache wants every ray of an 8x8 patch).  dfeat keeps the level-major layout of the whole ray set.
   // (r03 A/B: 1 / 2 / 4 / 8 chunks 5.96 / 5.65 / 5.64 / 6.00 ms, no overlap 6.33 ms; the switches were retired in r04.)
-  struct Side { hipStream_t s; hipEvent_t fork, join; };
-  static Side side[32] = {};
-  const bool fork = dfeat && last < lv.L && dev_id < 32;
-  NgpChunks plan = ngp_bwd_plan(N);                                            // (the entries buffer is sized for this chunking)
-  if (!(dfeat && last < lv.L)) { plan.n = 1; plan.start[0] = 0; plan.start[1] = N; }
-  const uint32_t n_chunks = plan.n;
-  const float thr_mlp = sf_fix_thr(4.0 * 256.0 * n_chunks);        // one addend per wave and launch: <= 256 workgroups x 4 waves per chunk
-  // The side stream and its fork / join events are ONE set per device: two host threads (or two caller streams) rendering on the
-  // same device would re-record each other's events, so the whole fork .. join section runs under the lock (host-side enqueue only:
-  // microseconds).  The guard below joins the side stream into the caller's stream on EVERY exit path, error returns included.
-  static std::mutex side_mu;
-  std::unique_lock<std::mutex> side_lk(side_mu, std::defer_lock);
-  struct SideJoin {
-    Side* sd = nullptr; hipStream_t st = nullptr; bool forked = false;
-    int join() { const bool f = forked; forked = false; return (!f || (hipEventRecord(sd->join, sd->s) == hipSuccess && hipStreamWaitEvent(st, sd->join, 0) == hipSuccess)) ? 0 : 1; }
-    ~SideJoin() { (void)join(); }
-  } side_join;
+  const bool fork = per_chunk && dev;
+  std::unique_lock<std::mutex> side_lk(g_bwd_side_mu, std::defer_lock);
+  SideJoin side_join;                               // (declared behind the lock: joins before the lock is released)
   if (fork) {
     side_lk.lock();
-    Side& sd = side[dev_id];
-    if (!sd.s && (hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking) != hipSuccess ||
-                  hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) != hipSuccess ||
-                  hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) != hipSuccess))
-      SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot create the side stream");
-    side_join.sd = &sd; side_join.st = st;
+    side_join.dev = dev; side_join.st = st;
   }
-  const uint32_t T2 = 2 * T;
-  for (uint32_t c = 0; c < n_chunks; ++c) {
+  for (uint32_t c = 0; c < plan.n; ++c) {
     const uint32_t n0 = plan.start[c], Nc = plan.start[c + 1] - n0;
     const uint32_t Pc = Nc * T2, P0 = n0 * T2;
     // matrix-core field backward of chunk c: one wave per 32 points and trip, six fp32 GEMMs on v_mfma_f32_16x16x4_f32 (ngp_bwd_mfma.h)
-    FBArgs a{};
-    a.table = f->embeddings; a.w0 = f->w0; a.b0 = f->b0; a.w1 = f->w1; a.b1 = f->b1; a.w2 = f->w2; a.b2 = f->b2; a.bound = f->bound;
-    a.g_w0 = acc_mlp + (segs.end[0] - tab_n); a.g_b0 = acc_mlp + (segs.end[1] - tab_n); a.g_w1 = acc_mlp + (segs.end[2] - tab_n);
-    a.g_b1 = acc_mlp + (segs.end[3] - tab_n); a.g_w2 = acc_mlp + (segs.end[4] - tab_n); a.g_b2 = acc_mlp + (segs.end[5] - tab_n);
-    a.f_w0 = g->g_w0; a.f_b0 = g->g_b0; a.f_w1 = g->g_w1; a.f_b1 = g->g_b1; a.f_w2 = g->g_w2; a.f_b2 = g->g_b2; a.thr = thr_mlp;
-    a.lv = lv;
-    a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3; a.aabb = aabb;
-    a.z_s = z_sorted + (size_t)P0; a.dsig = dsig + (size_t)P0; a.drgb = drgb + (size_t)P0 * 3; a.dfeat_out = dfeat;
-    a.P = Pc; a.T2 = T2; a.dfeat_P = (uint32_t)M; a.p_off = P0;
-    a.feat_c = field_cache;                           // (or all three null: the kernel re-gathers the features)
-    a.feat_f = field_cache ? field_cache + (size_t)N * T * NGP_FEAT : nullptr;
-    a.perm = field_cache ? reinterpret_cast<const uint32_t*>(field_cache + 2 * (size_t)N * T * NGP_FEAT) : nullptr;
-    const uint32_t trips = sf_div_up(Pc, FB_PTS);
-    const uint32_t grid = trips < 1024 ? sf_div_up(trips, 4) : 256;   // one resident workgroup per CU (LDS-bound), 4 waves each
+    a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3;
+    a.z_s = z_sorted + (size_t)P0; a.dsig = dsig + (size_t)P0; a.drgb = drgb + (size_t)P0 * 3;
+    a.P = Pc; a.p_off = P0;
+    const uint32_t grid = ngp_field_bwd_grid(Pc, FB_PTS);
     // with a field cache: k_ngp_field_bwd_pipe (ngp_bwd_pipe.h; same trips, same LDS image, same values) unless switched off
     const int pipe = field_cache && g_field_bwd_pipe.load(std::memory_order_relaxed) != 0 ? 1 : 0;
-    if (pipe) k_ngp_field_bwd_pipe<<<grid, 256, lds2, st>>>(a);
-    else k_ngp_field_bwd_mfma<<<grid, 256, lds2, st>>>(a);
+    if (pipe) k_ngp_field_bwd_pipe<<<grid, 256, FB_LDS_BYTES, st>>>(a);
+    else k_ngp_field_bwd_mfma<<<grid, 256, FB_LDS_BYTES, st>>>(a);
     SF_CHECK_LAUNCH(pipe ? "ngp_field_bwd_pipe" : "ngp_field_bwd_mfma");
     g_field_bwd_launches[pipe].fetch_add(1, std::memory_order_relaxed);
-    if (dfeat && last < lv.L) {
-      hipStream_t sf = st;
-      if (fork) {
-        Side& sd = side[dev_id];
-        if (hipEventRecord(sd.fork, st) != hipSuccess || hipStreamWaitEvent(sd.s, sd.fork, 0) != hipSuccess)
-          SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: fork failed");
-        sf = sd.s;
-        side_join.forked = true;
-      }
-      if (binned) {
-        SBArgs b{};
-        b.lv = lv; b.bound = f->bound; b.rays_o = a.rays_o; b.rays_d = a.rays_d; b.aabb = aabb; b.z_s = a.z_s; b.dfeat = dfeat;
-        b.gtable = acc_tab; b.gtable_f = g->g_embeddings; b.thr = thr_tab; b.cursor = bin_cursor; b.ent = bin_ent;
-        b.P = Pc; b.T2 = T2; b.first_level = first_bin; b.P_stride = (uint32_t)M; b.p_off = P0; b.cap = bin_cap;
-        SBRArgs r{};
-        r.lv = lv; r.gtable = acc_tab; r.gtable_f = g->g_embeddings; r.thr = thr_tab; r.cursor = bin_cursor; r.ent = bin_ent; r.first_level = first_bin; r.cap = bin_cap;
-        for (uint32_t l = 0; l <= NGP_MAX_LEVELS; ++l) { b.bucket0[l] = bucket0[l]; r.bucket0[l] = bucket0[l]; }
-        const uint32_t tiles = sf_div_up(Pc, SB_THREADS);
-        k_ngp_bin<<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
-        SF_CHECK_LAUNCH("ngp_bin");
-        k_ngp_bin_reduce<<<total_buckets, SBR_THREADS, 0, sf>>>(r);           // leaves the cursors at zero for the next chunk
-        SF_CHECK_LAUNCH("ngp_bin_reduce");
-      } else {
-        const uint64_t items = (uint64_t)4 * Pc * (lv.L - last);
-        const uint32_t grid_f = (uint32_t)(items / 256 < 16384 ? (items + 255) / 256 : 16384);
-        k_ngp_scatter_fine<<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, last,
-                                                   (uint32_t)M, P0);
-        SF_CHECK_LAUNCH("ngp_scatter_fine");
-      }
+    if (!per_chunk) continue;
+    if (fork && side_join.fork()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: fork failed");
+    hipStream_t sf = fork ? dev->side : st;
+    if (sp.binned) {
+      b.rays_o = a.rays_o; b.rays_d = a.rays_d; b.z_s = a.z_s; b.P = Pc; b.p_off = P0;
+      const uint32_t tiles = sf_div_up(Pc, SB_THREADS);
+      k_ngp_bin<<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
+      SF_CHECK_LAUNCH("ngp_bin");
+      k_ngp_bin_reduce<<<sp.total_buckets, SBR_THREADS, 0, sf>>>(r);         // leaves the cursors at zero for the next chunk
+      SF_CHECK_LAUNCH("ngp_bin_reduce");
+    } else {
+      const uint64_t items = (uint64_t)4 * Pc * (lv.L - sp.last);
+      const uint32_t grid_f = (uint32_t)(items / 256 < 16384 ? (items + 255) / 256 : 16384);
+      k_ngp_scatter_fine<<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, sp.last,
+                                                 (uint32_t)M, P0);
+      SF_CHECK_LAUNCH("ngp_scatter_fine");
     }
   }
-  if (dfeat && last > 0) {
+  if (dfeat && sp.last > 0) {
     const uint32_t grid_sc = sf_div_up(N, SC_RAYS);
-    k_ngp_scatter<1024><<<grid_sc, 1024, lds_sc, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, cached, last, sc_run);
+    k_ngp_scatter<1024><<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN);
     SF_CHECK_LAUNCH("ngp_scatter");
   }
   if (side_join.join()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: join failed");

@@ -23,13 +23,8 @@
 #pragma once
 #include "sf_dev.h"
 #include "ngp_device.h"
+#include "ngp_bwd_plan.h"                          // the buckets: SB_ROWS_LOG, SB_ROWS, SB_MAX_BUCKETS
 
-#ifndef SB_ROWS_LOG
-#define SB_ROWS_LOG 10          // measured on the reference field (2^16-row `tiled` levels), render fwd + bwd: 2048 / 1024 / 512 rows = 4.27 / 3.90 / 4.13 ms
-#endif
-#define SB_ROWS (1u << SB_ROWS_LOG)   // table rows per bucket
-static_assert(SB_ROWS_LOG <= 10, "the entry word keeps row1 - row0 + 1024 in 11 bits");
-#define SB_MAX_BUCKETS (1u << (19 - SB_ROWS_LOG))            // per level: hsize <= 2^19, the reference's log2_hashmap_size (larger tables keep k_ngp_scatter_fine)
 #define SB_THREADS 1024
 
 #ifdef SF_HOST_EMU

@@ -16,14 +16,10 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 // which lanes, waves and workgroups arrive, as fp32 / fp64 atomics' does; one conversion to fp32 at the end.  Every other
 // contribution (|v| >= thr, Inf, NaN) is added to the fp32 gradient with an fp32 atomic as before, so it is never clipped or
 // wrapped and a non-finite gradient stays visible.  The caller picks thr <= 2^18 / (most addends one sum can receive), so no
-// fixed-point sum reaches 2^18 in magnitude: the int64 never overflows (sf_fix_thr).
+// fixed-point sum reaches 2^18 in magnitude: the int64 never overflows (sf_fix_thr, sf_fix.h).
 #define SF_FIX_ONE 17592186044416.0            // 2^44
 #define SF_FIX_INV (1.0 / SF_FIX_ONE)
-static inline float sf_fix_thr(double max_addends) {      // host: largest power of two <= 2^18 / max_addends
-  float t = 262144.0f;
-  while (t > 0x1p-40f && (double)t * max_addends > 262144.0) t *= 0.5f;
-  return t;
-}
+#include "sf_fix.h"
 
 #ifdef SF_HOST_EMU
 #include "hip_emu.h"

@@ -16,7 +16,8 @@ def lib():
     if _lib is None:
         src = os.path.join(_HERE, "ngp_host.cpp")
         hdr = os.path.join(_HERE, "..", "..", "sparsefusion_amd", "csrc", "ngp_device.h")
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        deps = (src, hdr, os.path.join(_HERE, "ngp_emu_common.h"))
+        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(_SO), exist_ok=True)
             subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-mfma",
                                    "-mavx2", "-fopenmp", "-Wno-unknown-pragmas", src, "-o", _SO])

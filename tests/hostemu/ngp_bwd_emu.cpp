@@ -6,81 +6,43 @@
 #endif
 #define HIPEMU_IMPLEMENTATION
 #include "hip_emu.h"
-#include <vector>
-struct float2 { float x, y; };
-#include "../../sparsefusion_amd/csrc/ngp_bwd_mfma.h"
-
-static void fill_levels(NgpLevels* lv, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype) {
-  for (uint32_t l = 0; l < NGP_MAX_LEVELS; ++l) {
-    const bool on = l < L;
-    const float scale = on ? exp2f((float)l * S) * (float)H - 1.0f : 0.f;
-    lv->scale[l] = scale;
-    lv->resolution[l] = on ? (uint32_t)ceilf(scale) + 1 : 1;
-    lv->offset[l] = on ? (uint32_t)h_offsets[l] : 0;
-    lv->hsize[l] = on ? (uint32_t)(h_offsets[l + 1] - h_offsets[l]) : 1;
-  }
-  lv->L = L;
-  lv->gridtype = gridtype;
-}
+#define NGP_EMU_FIELD_BWD
+#include "ngp_emu_common.h"
+#include "../../sparsefusion_amd/csrc/ngp_bwd_plan.h"
 
 extern "C" void emu_field_bwd(const float* table, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype,
                               const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2,
                               float bound, const float* rays_o, const float* rays_d, const float* aabb, const float* z_s,
                               const float* dsig, const float* drgb, uint32_t P, uint32_t T2, uint32_t grid, int use_ref,
                               float* g_w0, float* g_b0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* dfeat) {
-  // use_ref == 2: the kernel on a field cache (features + permutation as the forward would leave them) instead of the re-gather
-  std::vector<float> fc, ff;
-  std::vector<uint32_t> perm;
-  if (use_ref == 2) {
-    NgpLevels lv0;
-    fill_levels(&lv0, h_offsets, L, S, H, gridtype);
-    const uint32_t T = T2 / 2, N = (P + T2 - 1) / T2;
-    fc.assign((size_t)N * T * NGP_FEAT, 0.f); ff.assign((size_t)N * T * NGP_FEAT, 0.f); perm.assign((size_t)N * T2, 0);
-    for (uint32_t p = 0; p < P; ++p) {
-      const uint32_t n = p / T2, m = p - n * T2;
-      const uint32_t src = (m * 7 + 3) % T2;                 // some permutation of the ray's samples (7 is odd, T2 a power of two... or coprime)
-      perm[p] = src;
-      float x[3], x01[3], feat[NGP_FEAT];
-      ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-      const bool inside = ngp_unit(x, bound, x01);
-      ngp_encode(lv0, table, x01, inside, feat);
-      float* row = src < T ? &fc[((size_t)n * T + src) * NGP_FEAT] : &ff[((size_t)n * T + (src - T)) * NGP_FEAT];
-      for (int i = 0; i < NGP_FEAT; ++i) row[i] = feat[i];
-    }
-  }
-  FBArgs a{};                                      // (feat_c / feat_f / perm stay null: the re-gather path)
-  a.table = table; a.w0 = w0; a.b0 = b0; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.bound = bound;
-  // the kernel sums its weight gradients in 64-bit fixed point (sf_dev.h); they are added to the float outputs as the product does
-  float* gout[6] = {g_w0, g_b0, g_w1, g_b1, g_w2, g_b2};
-  const int glen[6] = {NGP_HID * NGP_FEAT, NGP_HID, NGP_HID * NGP_HID, NGP_HID, NGP_OUT * NGP_HID, NGP_OUT};
-  std::vector<long long> gacc[6];
-  for (int k = 0; k < 6; ++k) gacc[k].assign(glen[k], 0);
-  a.g_w0 = gacc[0].data(); a.g_b0 = gacc[1].data(); a.g_w1 = gacc[2].data(); a.g_b1 = gacc[3].data(); a.g_w2 = gacc[4].data(); a.g_b2 = gacc[5].data();
-  a.f_w0 = g_w0; a.f_b0 = g_b0; a.f_w1 = g_w1; a.f_b1 = g_b1; a.f_w2 = g_w2; a.f_b2 = g_b2;
-  a.thr = sf_fix_thr(4.0 * grid);                  // one addend per wave, as the product's bound
-  fill_levels(&a.lv, h_offsets, L, S, H, gridtype);
-  a.rays_o = rays_o; a.rays_d = rays_d; a.aabb = aabb; a.z_s = z_s; a.dsig = dsig; a.drgb = drgb; a.dfeat_out = dfeat; a.dfeat_P = P; a.p_off = 0;
-  a.P = P; a.T2 = T2;
-  if (use_ref == 2) { a.feat_c = fc.data(); a.feat_f = ff.data(); a.perm = perm.data(); }
+  NgpLevels lv;
+  fill_levels(&lv, h_offsets, L, S, H, gridtype);
   if (use_ref != 1) {
+    // use_ref == 2: the kernel on a field cache (features + permutation as the forward would leave them) instead of the re-gather
+    EmuFieldCache cache;
+    if (use_ref == 2) {
+      std::vector<float> feat((size_t)P * NGP_FEAT);
+      emu_encode_points(lv, table, bound, rays_o, rays_d, aabb, z_s, P, T2, feat.data(), nullptr, nullptr);
+      cache.build(feat.data(), P, T2);
+    }
+    EmuFixAcc acc(g_w0, g_b0, g_w1, g_b1, g_w2, g_b2);
+    // thr: one addend per wave, as the product's bound
+    FBArgs a = emu_fb_args(lv, table, w0, b0, w1, b1, w2, b2, bound, acc, sf_fix_thr(4.0 * grid), rays_o, rays_d, aabb, z_s, dsig, drgb, dfeat, 0,
+                           P / T2, T2, P, use_ref == 2 ? &cache : nullptr);
+    a.P = P;
     hipemu::launch(grid, 256, FB_LDS_FLOATS * sizeof(float), [&] { k_ngp_field_bwd_mfma(a); });
-    for (int k = 0; k < 6; ++k)
-      for (int i = 0; i < glen[k]; ++i) gout[k][i] += (float)((double)gacc[k][i] * SF_FIX_INV);
+    acc.convert();
     return;
   }
   // reference: per-point math (ngp_device.h), serial
-  std::vector<float> W(NGP_WTOTAL);
-  for (int i = 0; i < NGP_HID * NGP_FEAT; ++i) W[NGP_W0 + i] = w0[i];
-  for (int i = 0; i < NGP_HID * NGP_HID; ++i) W[NGP_W1 + i] = w1[i];
-  for (int i = 0; i < NGP_OUT * NGP_HID; ++i) W[NGP_W2 + i] = w2[i];
-  for (int i = 0; i < NGP_HID; ++i) { W[NGP_B0 + i] = b0[i]; W[NGP_B1 + i] = b1[i]; }
-  for (int i = 0; i < NGP_OUT; ++i) W[NGP_B2 + i] = b2[i];
+  std::vector<float> W;
+  pack_weights(W, w0, b0, w1, b1, w2, b2);
   for (uint32_t p = 0; p < P; ++p) {
     const uint32_t n = p / T2;
     float x[3], x01[3], feat[NGP_FEAT], h1[NGP_HID], h2[NGP_HID], out[NGP_OUT], dout[NGP_OUT];
     ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
     const bool inside = ngp_unit(x, bound, x01);
-    ngp_encode(a.lv, table, x01, inside, feat);
+    ngp_encode(lv, table, x01, inside, feat);
     ngp_mlp_forward(W.data(), feat, h1, h2, out);
     const float pre = out[0] + ngp_blob(x);
     dout[0] = dsig[p] * expf(fminf(fmaxf(pre, -15.0f), 15.0f));
@@ -105,15 +67,7 @@ extern "C" void emu_features(const float* table, const int32_t* h_offsets, uint3
                              float* feat, float* xyz, float* inside_out) {
   NgpLevels lv;
   fill_levels(&lv, h_offsets, L, S, H, gridtype);
-  for (uint32_t p = 0; p < P; ++p) {
-    const uint32_t n = p / T2;
-    float x[3], x01[3];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    const bool inside = ngp_unit(x, bound, x01);
-    ngp_encode(lv, table, x01, inside, feat + (size_t)p * NGP_FEAT);
-    for (int i = 0; i < 3; ++i) xyz[p * 3 + i] = x[i];
-    inside_out[p] = inside ? 1.0f : 0.0f;
-  }
+  emu_encode_points(lv, table, bound, rays_o, rays_d, aabb, z_s, P, T2, feat, xyz, inside_out);
 }
 
 extern "C" void emu_field_bwd_chunks(const float* table, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype,
@@ -122,38 +76,38 @@ extern "C" void emu_field_bwd_chunks(const float* table, const int32_t* h_offset
                                      const float* dsig, const float* drgb, uint32_t N, uint32_t T2, uint32_t n_chunks, const uint32_t* start,
                                      const uint32_t* grids, float thr, const float* feat_sorted,
                                      float* g_w0, float* g_b0, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* dfeat) {
-  const uint32_t P = N * T2, T = T2 / 2;
-  std::vector<float> fc, ff;
-  std::vector<uint32_t> perm;
-  if (feat_sorted) {                               // a field cache holding the given rows behind some permutation of every ray's samples
-    fc.assign((size_t)N * T * NGP_FEAT, 0.f); ff.assign((size_t)N * T * NGP_FEAT, 0.f); perm.assign((size_t)N * T2, 0);
-    for (uint32_t p = 0; p < P; ++p) {
-      const uint32_t n = p / T2, m = p - n * T2, src = (m * 7 + 3) % T2;
-      perm[p] = src;
-      float* row = src < T ? &fc[((size_t)n * T + src) * NGP_FEAT] : &ff[((size_t)n * T + (src - T)) * NGP_FEAT];
-      for (int i = 0; i < NGP_FEAT; ++i) row[i] = feat_sorted[(size_t)p * NGP_FEAT + i];
-    }
-  }
-  float* gout[6] = {g_w0, g_b0, g_w1, g_b1, g_w2, g_b2};
-  const int glen[6] = {NGP_HID * NGP_FEAT, NGP_HID, NGP_HID * NGP_HID, NGP_HID, NGP_OUT * NGP_HID, NGP_OUT};
-  std::vector<long long> gacc[6];
-  for (int k = 0; k < 6; ++k) gacc[k].assign(glen[k], 0);
+  const uint32_t P = N * T2;
+  NgpLevels lv;
+  fill_levels(&lv, h_offsets, L, S, H, gridtype);
+  EmuFieldCache cache;
+  if (feat_sorted) cache.build(feat_sorted, P, T2);            // a field cache holding the given rows
+  EmuFixAcc acc(g_w0, g_b0, g_w1, g_b1, g_w2, g_b2);
   for (uint32_t c = 0; c < n_chunks; ++c) {
-    const uint32_t n0 = start[c], Nc = start[c + 1] - n0, P0 = n0 * T2;
-    FBArgs a{};
-    a.table = table; a.w0 = w0; a.b0 = b0; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.bound = bound;
-    a.g_w0 = gacc[0].data(); a.g_b0 = gacc[1].data(); a.g_w1 = gacc[2].data(); a.g_b1 = gacc[3].data(); a.g_w2 = gacc[4].data(); a.g_b2 = gacc[5].data();
-    a.f_w0 = g_w0; a.f_b0 = g_b0; a.f_w1 = g_w1; a.f_b1 = g_b1; a.f_w2 = g_w2; a.f_b2 = g_b2;
-    a.thr = thr;
-    fill_levels(&a.lv, h_offsets, L, S, H, gridtype);
-    a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3; a.aabb = aabb;
-    a.z_s = z_s + P0; a.dsig = dsig + P0; a.drgb = drgb + (size_t)P0 * 3; a.dfeat_out = dfeat;
-    a.P = Nc * T2; a.T2 = T2; a.dfeat_P = P; a.p_off = P0;
-    if (feat_sorted) { a.feat_c = fc.data(); a.feat_f = ff.data(); a.perm = perm.data(); }
+    const FBArgs a = emu_fb_args(lv, table, w0, b0, w1, b1, w2, b2, bound, acc, thr, rays_o, rays_d, aabb, z_s, dsig, drgb, dfeat, start[c],
+                                 start[c + 1] - start[c], T2, P, feat_sorted ? &cache : nullptr);
     hipemu::launch(grids[c], 256, FB_LDS_FLOATS * sizeof(float), [&] { k_ngp_field_bwd_mfma(a); });
   }
-  for (int k = 0; k < 6; ++k)
-    for (int i = 0; i < glen[k]; ++i) gout[k][i] += (float)((double)gacc[k][i] * SF_FIX_INV);
+  acc.convert();
+}
+
+// ---- the host plan of sf_ngp_render_backward (sparsefusion_amd/csrc/ngp_bwd_plan.h) as the product calls it, for the restatement of
+// tests/ngp_bwd_cases.py.  start: room for 66 words.  emu_scatter_plan's out: cached, first_bin, binned, last, total_buckets, bin_cap,
+// then bucket0[NGP_MAX_LEVELS + 1].
+extern "C" void emu_bwd_plan(uint32_t N, uint32_t* n, uint32_t* max_rays, uint32_t* start) {
+  const NgpChunks c = ngp_bwd_plan(N);
+  *n = c.n; *max_rays = c.max_rays;
+  for (uint32_t i = 0; i < 66; ++i) start[i] = c.start[i];
+}
+extern "C" uint32_t emu_field_bwd_grid(uint32_t P) { return ngp_field_bwd_grid(P, FB_PTS); }
+extern "C" float emu_bwd_thr_mlp(uint32_t n_chunks) { return ngp_bwd_thr_mlp(n_chunks); }
+extern "C" void emu_scatter_plan(const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype, int table_grad, uint32_t N,
+                                 uint32_t T, uint32_t* out) {
+  NgpLevels lv;
+  fill_levels(&lv, h_offsets, L, S, H, gridtype);
+  const NgpScatterPlan s = ngp_scatter_plan(lv, table_grad != 0, N, T);
+  const uint32_t head[6] = {s.cached, s.first_bin, s.binned ? 1u : 0u, s.last, s.total_buckets, s.bin_cap};
+  for (int i = 0; i < 6; ++i) out[i] = head[i];
+  for (uint32_t l = 0; l <= NGP_MAX_LEVELS; ++l) out[6 + l] = s.bucket0[l];
 }
 
 // ---- binned table-gradient scatter (sparsefusion_amd/csrc/ngp_scatter_bin.h) against ngp_scatter (ngp_device.h), levels

@@ -6,22 +6,8 @@
 #endif
 #define HIPEMU_IMPLEMENTATION
 #include "hip_emu.h"
-#include <vector>
-struct float2 { float x, y; };
+#include "ngp_emu_common.h"
 #include "../../sparsefusion_amd/csrc/ngp_field_mfma.h"
-
-static void fill_levels(NgpLevels* lv, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype) {
-  for (uint32_t l = 0; l < NGP_MAX_LEVELS; ++l) {
-    const bool on = l < L;
-    const float scale = on ? exp2f((float)l * S) * (float)H - 1.0f : 0.f;
-    lv->scale[l] = scale;
-    lv->resolution[l] = on ? (uint32_t)ceilf(scale) + 1 : 1;
-    lv->offset[l] = on ? (uint32_t)h_offsets[l] : 0;
-    lv->hsize[l] = on ? (uint32_t)(h_offsets[l + 1] - h_offsets[l]) : 1;
-  }
-  lv->L = L;
-  lv->gridtype = gridtype;
-}
 
 // mode 0: z from (nears, fars, lin, u) and written to z_out; mode 1: z read from z_in.  use_ref: the per-point math, serial.
 // feat_out may be null.  P = N * T.
@@ -42,12 +28,8 @@ extern "C" void emu_field_fwd(int mode, const float* table, const int32_t* h_off
     else hipemu::launch(grid, 256, FM_LDS_FLOATS * sizeof(float), [&] { k_ngp_field_mfma<1>(a); });
     return;
   }
-  std::vector<float> W(NGP_WTOTAL);
-  for (int i = 0; i < NGP_HID * NGP_FEAT; ++i) W[NGP_W0 + i] = w0[i];
-  for (int i = 0; i < NGP_HID * NGP_HID; ++i) W[NGP_W1 + i] = w1[i];
-  for (int i = 0; i < NGP_OUT * NGP_HID; ++i) W[NGP_W2 + i] = w2[i];
-  for (int i = 0; i < NGP_HID; ++i) { W[NGP_B0 + i] = b0[i]; W[NGP_B1 + i] = b1[i]; }
-  for (int i = 0; i < NGP_OUT; ++i) W[NGP_B2 + i] = b2[i];
+  std::vector<float> W;
+  pack_weights(W, w0, b0, w1, b1, w2, b2);
   for (uint32_t p = 0; p < P; ++p) {                    // the body of k_ngp_field<0 / 1> (ngp_render.hip)
     const uint32_t n = p / T, k = p - n * T;
     float z;

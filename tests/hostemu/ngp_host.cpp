@@ -2,35 +2,8 @@
 // (sparsefusion_amd/csrc/ngp_device.h) with g++ and runs them thread by thread, so the kernel logic
 // can be checked against the oracle on a machine without a GPU.  TEST INFRASTRUCTURE ONLY -- never
 // loaded by the sparsefusion_amd package.
-#include <math.h>
-#include <stdint.h>
 #include <stdlib.h>
-#include <string.h>
-#include <vector>
-struct float2 { float x, y; };
-#include "../../sparsefusion_amd/csrc/ngp_device.h"
-
-static void fill_levels(NgpLevels* lv, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype) {
-  memset(lv, 0, sizeof(*lv));
-  for (uint32_t l = 0; l < NGP_MAX_LEVELS; ++l) {
-    if (l < L) {
-      const float scale = exp2f((float)l * S) * (float)H - 1.0f;
-      lv->scale[l] = scale;
-      lv->resolution[l] = (uint32_t)ceil(scale) + 1;
-      lv->offset[l] = (uint32_t)h_offsets[l];
-      lv->hsize[l] = (uint32_t)(h_offsets[l + 1] - h_offsets[l]);
-    } else { lv->resolution[l] = 1; lv->hsize[l] = 1; }
-  }
-  lv->L = L; lv->gridtype = gridtype;
-}
-
-static void pack_weights(std::vector<float>& W, const float* w0, const float* b0, const float* w1, const float* b1,
-                         const float* w2, const float* b2) {
-  W.resize(NGP_WTOTAL);
-  memcpy(&W[NGP_W0], w0, sizeof(float) * NGP_HID * NGP_FEAT); memcpy(&W[NGP_B0], b0, sizeof(float) * NGP_HID);
-  memcpy(&W[NGP_W1], w1, sizeof(float) * NGP_HID * NGP_HID);  memcpy(&W[NGP_B1], b1, sizeof(float) * NGP_HID);
-  memcpy(&W[NGP_W2], w2, sizeof(float) * NGP_OUT * NGP_HID);  memcpy(&W[NGP_B2], b2, sizeof(float) * NGP_OUT);
-}
+#include "ngp_emu_common.h"                        // fill_levels, pack_weights
 
 static void near_far(const float* o, const float* d, const float* aabb, float min_near, float* pn, float* pf) {
   const float rdx = 1 / d[0], rdy = 1 / d[1], rdz = 1 / d[2];

@@ -78,9 +78,10 @@ C008 = f32(0.08)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# sf_ngp_render_backward's launch geometry (sparsefusion_amd/csrc/ngp_render.hip), restated.  tests/test_plans_cpu.py checks it against CASES.
+# sf_ngp_render_backward's launch geometry (sparsefusion_amd/csrc/ngp_bwd_plan.h), restated.  tests/test_plans_cpu.py checks it against CASES,
+# tests/test_hostemu_ngp_bwd.py against the C++ functions themselves.
 def fix_thr(max_addends):
-    """sf_fix_thr (sf_dev.h): the largest power of two <= 2^18 / max_addends."""
+    """sf_fix_thr (sf_fix.h): the largest power of two <= 2^18 / max_addends."""
     t = 262144.0
     while t > 2.0 ** -40 and t * max_addends > 262144.0:
         t *= 0.5

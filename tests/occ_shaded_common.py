@@ -241,7 +241,7 @@ def _emu():
     global _handle
     if _handle is None:
         csrc = os.path.join(_HERE, "..", "..", "sparsefusion_amd", "csrc")
-        deps = [os.path.join(_HERE, f) for f in ("occ_shade_emu.cpp", "ngp_host.cpp", "hip_emu.h")] + \
+        deps = [os.path.join(_HERE, f) for f in ("occ_shade_emu.cpp", "ngp_host.cpp", "ngp_emu_common.h", "hip_emu.h")] + \
                [os.path.join(csrc, f) for f in ("ngp_occ_shade.h", "occ_marcher.h", "ngp_point_attrs.h", "ngp_device.h", "sf_dev.h")]
         if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(s) for s in deps):
             os.makedirs(os.path.dirname(_SO), exist_ok=True)

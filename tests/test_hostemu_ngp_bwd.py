@@ -19,8 +19,9 @@ pytestmark = pytest.mark.skipif(not fused.available(), reason="host clang not fo
 
 
 def _lib():
-    srcs = [os.path.join(HERE, "ngp_bwd_emu.cpp"), os.path.join(HERE, "hip_emu.h")] + \
-           [os.path.join(HERE, "..", "..", "sparsefusion_amd", "csrc", f) for f in ("ngp_bwd_mfma.h", "ngp_scatter_bin.h", "ngp_device.h", "sf_dev.h")]
+    srcs = [os.path.join(HERE, "ngp_bwd_emu.cpp"), os.path.join(HERE, "hip_emu.h"), os.path.join(HERE, "ngp_emu_common.h")] + \
+           [os.path.join(HERE, "..", "..", "sparsefusion_amd", "csrc", f)
+            for f in ("ngp_bwd_mfma.h", "ngp_scatter_bin.h", "ngp_bwd_plan.h", "ngp_device.h", "sf_dev.h", "sf_fix.h")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(SO), exist_ok=True)
         subprocess.check_call([fused.CLANG, "-std=c++17", "-O2", "-fPIC", "-shared", "-I" + HERE, "-Wall", "-Wno-unused-function",
@@ -223,3 +224,67 @@ def test_binned_scatter_keeps_large_and_non_finite_contributions():
     assert bool(nan_g.any()) and not bool((nan_g & ~nan_r).any())      # NaN where the reference has it (a zero-weight corner may be skipped)
     ok = ~nan_r
     assert float((got[ok] - ref[ok]).abs().max()) / float(ref[ok].abs().max()) < 1e-5
+
+
+def _c_plan(lib, N):
+    n, max_rays, start = C.c_uint32(0), C.c_uint32(0), (C.c_uint32 * 66)()
+    lib.emu_bwd_plan(C.c_uint32(N), C.byref(n), C.byref(max_rays), start)
+    return n.value, max_rays.value, list(start[:n.value + 1])
+
+
+def test_host_plan_matches_the_restatement():
+    """ngp_bwd_plan, the field backward's grid rule and the thr_mlp rule of csrc/ngp_bwd_plan.h -- the functions sf_ngp_render_backward calls,
+    exported by the harness -- against tests/ngp_bwd_cases.py's restatement (bwd_plan; chunk, grid and thr of bwd_geometry), with ==: the ray
+    counts of CASES, the counts around every branch of the plan, every multiple of 256 up to 70000."""
+    lib = _lib()
+    lib.emu_field_bwd_grid.restype = C.c_uint32
+    lib.emu_bwd_thr_mlp.restype = C.c_float
+    Ns = {c["N"]: c["T"] for c in ngp_bwd_cases.CASES.values()}
+    for N in [1, 37, 2048, 4096, 10000, 16384, 32768, 40000, 51712, 65535, 65536] + list(range(256, 70001, 256)):
+        Ns.setdefault(N, 4)
+    for N, T in Ns.items():
+        n, max_rays, start = _c_plan(lib, N)
+        assert start == ngp_bwd_cases.bwd_plan(N), N
+        assert 1 <= n <= 64 and start[0] == 0 and start[-1] == N and all(a < b for a, b in zip(start, start[1:])), (N, start)
+        assert all(b - a <= max_rays for a, b in zip(start, start[1:])), (N, max_rays, start)
+        geo = ngp_bwd_cases.bwd_geometry(N, T)
+        assert [p0 for p0, *_ in geo["chunks"]] == [s * 2 * T for s in start[:-1]] and [P for _, P, *_ in geo["chunks"]] == \
+            [(b - a) * 2 * T for a, b in zip(start, start[1:])], N
+        assert [g for *_, g in geo["chunks"]] == [lib.emu_field_bwd_grid(C.c_uint32(P)) for _, P, *_ in geo["chunks"]], N
+        assert geo["thr"] == lib.emu_bwd_thr_mlp(C.c_uint32(n)), N
+
+
+def _c_scatter_plan(lib, offs, L, S, table_grad, N, T):
+    out = (C.c_uint32 * (6 + 17))()
+    offs = offs.to(torch.int32).contiguous()
+    lib.emu_scatter_plan(C.c_void_p(offs.data_ptr()), C.c_uint32(L), C.c_float(S), C.c_uint32(16), C.c_uint32(1), C.c_int(table_grad),
+                         C.c_uint32(N), C.c_uint32(T), out)
+    return dict(cached=out[0], first_bin=out[1], binned=bool(out[2]), last=out[3], total_buckets=out[4], bin_cap=out[5], bucket0=list(out[6:]))
+
+
+def test_scatter_plan_on_the_reference_levels_and_on_an_oversized_level():
+    """ngp_scatter_plan (csrc/ngp_bwd_plan.h) on the reference field's 16 levels at H = 16: with a table gradient the hashed levels are binned
+    (the numbers follow from the scales, the cut-offs 60 and 640 and 1024-row buckets), without one every level is k_ngp_scatter's; a level set
+    with one level of more than SB_MAX_BUCKETS = 512 buckets keeps the atomics (binned == false)."""
+    lib = _lib()
+    p = ngp_ref.init_params(bound=4, seed=3, table_std=0.5, sigma_bias=-1.0)
+    offs = p["encoder.offsets"].to(torch.int64)
+    L, S, N, T = offs.numel() - 1, float(np.log2(ngp_ref.per_level_scale(4))), 16384, 64
+    assert L == 16
+    scale = [float(np.float32(np.exp2(np.float32(l) * np.float32(S)) * np.float32(16) - np.float32(1))) for l in range(L)]
+    n60, n640 = sum(s <= 60.0 for s in scale), sum(s <= 640.0 for s in scale)
+    assert 0 < n60 < n640 <= L
+    hsize = [int(offs[l + 1] - offs[l]) for l in range(L)]
+    sp = _c_scatter_plan(lib, offs, L, S, 1, N, T)
+    assert sp["binned"] and sp["cached"] <= sp["first_bin"] and sp["last"] == sp["first_bin"]
+    assert sp["first_bin"] == n60 and sp["cached"] == n60
+    nb = [(hsize[l] + 1023) // 1024 if l >= n60 else 0 for l in range(L)]
+    assert sp["bucket0"] == [sum(nb[:l]) for l in range(L + 1)] and sp["total_buckets"] == sum(nb)
+    max_rays = max(b - a for a, b in zip(ngp_bwd_cases.bwd_plan(N), ngp_bwd_cases.bwd_plan(N)[1:]))
+    assert sp["bin_cap"] == (max_rays * 2 * T * 4 * 24 + 16 * 512 * 64) // sum(nb)
+    sp0 = _c_scatter_plan(lib, offs, L, S, 0, N, T)
+    assert sp0["last"] == L and not sp0["binned"] and sp0["first_bin"] == L and sp0["cached"] == n640 and sp0["bin_cap"] == 0
+    big = offs.clone()
+    big[L:] += (1 << 19) + 1024 - hsize[L - 1]               # the last level: 513 buckets
+    spb = _c_scatter_plan(lib, big, L, S, 1, N, T)
+    assert not spb["binned"] and spb["first_bin"] == L and spb["cached"] == n640 and spb["last"] == n640 and spb["bin_cap"] == 0

@@ -24,7 +24,7 @@ NAMES = ("g_w0", "g_b0", "g_w1", "g_b1", "g_w2", "g_b2", "dfeat")
 
 
 def _lib():
-    srcs = [os.path.join(HERE, "ngp_bwd_pipe_emu.cpp"), os.path.join(HERE, "hip_emu.h")] + \
+    srcs = [os.path.join(HERE, "ngp_bwd_pipe_emu.cpp"), os.path.join(HERE, "hip_emu.h"), os.path.join(HERE, "ngp_emu_common.h")] + \
            [os.path.join(HERE, "..", "..", "sparsefusion_amd", "csrc", f) for f in ("ngp_bwd_pipe.h", "ngp_bwd_mfma.h", "ngp_device.h", "sf_dev.h")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(SO), exist_ok=True)

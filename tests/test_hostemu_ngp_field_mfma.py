@@ -21,7 +21,7 @@ FLT_MAX = 3.402823466e+38
 
 
 def _lib():
-    srcs = [os.path.join(HERE, "ngp_field_mfma_emu.cpp"), os.path.join(HERE, "hip_emu.h")] + \
+    srcs = [os.path.join(HERE, "ngp_field_mfma_emu.cpp"), os.path.join(HERE, "hip_emu.h"), os.path.join(HERE, "ngp_emu_common.h")] + \
            [os.path.join(HERE, "..", "..", "sparsefusion_amd", "csrc", f) for f in ("ngp_field_mfma.h", "ngp_device.h", "sf_dev.h")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(SO), exist_ok=True)

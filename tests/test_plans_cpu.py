@@ -596,7 +596,7 @@ def test_softmax_reference_alone_stays_under_the_mismatch_cap(N):
 
 
 def test_ngp_bwd_geometry_restatement_matches_the_cases():
-    """tests/ngp_bwd_cases.py restates sf_ngp_render_backward's launch geometry (ngp_bwd_plan's chunks, grid = trips < 1024 ? ceil(trips / 4) : 256,
+    """tests/ngp_bwd_cases.py restates sf_ngp_render_backward's launch geometry (csrc/ngp_bwd_plan.h: ngp_bwd_plan's chunks, grid = trips < 1024 ? ceil(trips / 4) : 256,
     wave 4 b + w takes trips 4 b + w + 4 grid i, thr_mlp = sf_fix_thr(1024 chunks)): the numbers the GPU cases of tests/test_gpu_ngp_bwd.py are
     written for, the constants of the C++ source the restatement copies, and the wave a point lands in."""
     import ngp_bwd_cases as nb
@@ -615,12 +615,15 @@ def test_ngp_bwd_geometry_restatement_matches_the_cases():
     assert int((geo["wave"] == 25).sum()) == 814 - 25 * 32 == 14 and int((geo["wave"] == 27).sum()) == 0
     assert nb.bwd_plan(16384) == [0, 8192, 16384] and nb.bwd_plan(40000) == [0, 8192, 16384, 24576, 32768, 40000] and nb.bwd_plan(2048) == [0, 2048]
     assert nb.bwd_plan(32768) == [0, 8192, 16384, 24576, 32768] and nb.bwd_plan(51712)[:2] == [0, 8192] and len(nb.bwd_plan(51712)) == 8
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "sparsefusion_amd", "csrc", "ngp_render.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "sparsefusion_amd", "csrc", "ngp_bwd_plan.h")).read()
     for needle in ("#define NGP_BWD_CHUNKS 2u", "const uint32_t grid = trips < 1024 ? sf_div_up(trips, 4) : 256;", "sf_fix_thr(4.0 * 256.0 * n_chunks)",
                    "(rays / k) % 256 == 0 && rays / k >= 2048", "for (uint32_t k = (N + 8191) / 8192; k > NGP_BWD_CHUNKS && k <= 64; ++k)"):
         assert needle in src, needle
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "sparsefusion_amd", "csrc", "ngp_bwd_mfma.h")).read()
     assert "#define FB_PTS 32" in hdr and "trip = blockIdx.x * 4 + wave; trip < n_trips; trip += gridDim.x * 4" in hdr
+    pipe = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "sparsefusion_amd", "csrc", "ngp_bwd_pipe.h")).read()
+    for needle in ("stride = gridDim.x * 4;", "uint32_t trip = blockIdx.x * 4 + wave;", "for (; trip < n_trips; trip += stride) {"):
+        assert needle in pipe, needle
     assert nb.fix_thr(1024.0) == 256.0 and nb.fix_thr(12.0) == 16384.0
 
 

@@ -161,7 +161,7 @@ def _emu():
     global _handle
     if _handle is None:
         csrc = os.path.join(_HERE, "..", "..", "sparsefusion_amd", "csrc")
-        deps = [os.path.join(_HERE, "texture_emu.cpp"), os.path.join(_HERE, "ngp_host.cpp"),
+        deps = [os.path.join(_HERE, "texture_emu.cpp"), os.path.join(_HERE, "ngp_host.cpp"), os.path.join(_HERE, "ngp_emu_common.h"),
                 os.path.join(csrc, "ngp_texture.h"), os.path.join(csrc, "ngp_device.h")]
         if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(_SO), exist_ok=True)

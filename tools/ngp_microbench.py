@@ -2,7 +2,8 @@
 --shading lambertian adds, after the default output: the shaded render (sf_ngp_render_shaded_forward), the albedo forward at the same
 size, and the composed route (albedo forward + sf_ngp_point_attrs over the sorted points + torch glue for the weights and the sums),
 each the median of 5 torch-event timings after a warm-up.
---bwd-pipe 0|1 selects the kernel of the cached field backward (renderer._FIELD_BWD_PIPE) instead of the default."""
+--bwd-pipe 0|1 selects the kernel of the cached field backward (renderer._FIELD_BWD_PIPE) instead of the default.
+--feat-cache 0|1 sets renderer._FEAT_CACHE: 0 = no field cache, the backward re-gathers the features (k_ngp_field_bwd_mfma)."""
 import os
 import sys
 import time
@@ -17,6 +18,10 @@ if "--bwd-pipe" in sys.argv:
     from sparsefusion_amd.nerf import renderer as _R
     _R._FIELD_BWD_PIPE = sys.argv[sys.argv.index("--bwd-pipe") + 1] == "1"
     print(f"field backward  : {'k_ngp_field_bwd_pipe' if _R._FIELD_BWD_PIPE else 'k_ngp_field_bwd_mfma'}")
+if "--feat-cache" in sys.argv:
+    from sparsefusion_amd.nerf import renderer as _R
+    _R._FEAT_CACHE = sys.argv[sys.argv.index("--feat-cache") + 1] == "1"
+    print(f"field cache     : {'kept by the forward' if _R._FEAT_CACHE else 'none (the backward re-gathers the features)'}")
 dev = "cuda:0"
 p = ngp_ref.init_params(bound=4, seed=1, table_std=0.5, sigma_bias=-3.0)
 net = NeRFNetwork(get_default_torch_ngp_opt())
