@@ -194,7 +194,9 @@ class LPIPS(PlanOwner, nn.Module):
         self._weights_loaded = False
 
     def invalidate(self):
-        self._pack_cache, self._plans = None, {}
+        # a live autograd context still holds the old backward plan (and, after set_operand, would run it on the other operand library):
+        # advancing the serial makes that backward raise like one after another forward
+        self._pack_cache, self._plans, self._serial = None, {}, self._serial + 1
 
     def set_operand(self, operand, grad_scale=None):
         """operand: None | "bf16" | "f16" (the IEEE-half build of the library, libsparsefusion_hip_f16.so); grad_scale: see __init__

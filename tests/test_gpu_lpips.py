@@ -152,3 +152,16 @@ def test_perceptual_loss_wrapper_and_errors():
     _ = loss.model(p, b.permute(0, 3, 1, 2))
     with pytest.raises(RuntimeError):
         d1.sum().backward()                                           # stale: a later forward reused the arena
+    # stale in another way: the module changed under a live autograd context, whose backward plan belongs to the old operand library / weights
+    d2 = loss.model(p, b.permute(0, 3, 1, 2))
+    loss.model.set_operand("f16")
+    with pytest.raises(RuntimeError, match="backward after another forward"):
+        d2.sum().backward()
+    loss.model.set_operand(None)
+    d3 = loss.model(p, b.permute(0, 3, 1, 2))
+    loss.model.load_state_dict(loss.model.state_dict())
+    with pytest.raises(RuntimeError, match="backward after another forward"):
+        d3.sum().backward()
+    p.grad = None
+    loss.model(p, b.permute(0, 3, 1, 2)).sum().backward()           # and a fresh forward / backward pair works after either
+    assert torch.isfinite(p.grad).all() and float(p.grad.abs().sum()) > 0
