@@ -105,10 +105,12 @@ def silu64(y, dy):
     return s, (sg * (1 + y * (1 - sg))).abs() * dy + dy * dy / 4 + (y.abs() + 6) * U24 * s.abs()
 
 
-def gn_act_ref64(x1, x2, s2_scale, G, gamma, beta, eps, counts, ss=None, silu=True, dx1=None):
+def gn_act_ref64(x1, x2, s2_scale, G, gamma, beta, eps, counts, ss=None, silu=True, dx1=None, stats=None):
     """x1 [B, HW, C1] (float64: the exact value of the first source; dx1 its uncertainty when it is evaluated lazily), x2 [B, HW, C2] fp32 or
     None, ss = (scale [B, C], shift [B, C]) or None, counts = stat_counts(...).  Returns want, delta [B, HW, C], the float64 (sum, sum of
-    squares) per (image, group) [B, G, 2] and their bound."""
+    squares) per (image, group) [B, G, 2] and their bound.  stats [B, G, 2] float64 = the ready-made statistics an op with flag 2 READ
+    (tests/vae_plan_cases.py): want is then evaluated on them, exactly as k_gn_apply does, and they add nothing to delta; the sums returned
+    are still those of the tensor, under `counts`."""
     B, HW, C1 = x1.shape
     C = C1 + (x2.shape[2] if x2 is not None else 0)
     Cg, n = C // G, HW * (C // G)
@@ -127,6 +129,8 @@ def gn_act_ref64(x1, x2, s2_scale, G, gamma, beta, eps, counts, ss=None, silu=Tr
         d_s1 = n_sum * U24 * sa + grp(dx).sum((0, 2))
         d_s2 = n_sq * U24 * s2 + 2 * grp(x.abs() * dx).sum((0, 2))
         sums[b], sums_bound[b] = torch.stack([s1, s2], -1), torch.stack([d_s1, d_s2], -1)
+        if stats is not None:
+            s1, s2, d_s1, d_s2 = stats[b, :, 0].double(), stats[b, :, 1].double(), torch.zeros_like(d_s1), torch.zeros_like(d_s2)
         mean, ex2 = s1 / n, s2 / n
         var = (ex2 - mean * mean).clamp(min=0)
         mean32, var32 = mean.float().double(), var.float().double()       # the kernel's rounding points
