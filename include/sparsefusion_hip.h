@@ -350,6 +350,46 @@ int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* rays_o, con
                                  float* workspace, uint64_t workspace_bytes, void* stream);
 uint64_t sf_ngp_render_shaded_workspace_bytes(uint32_t N, uint32_t T);
 
+/* The shaded render WITH a backward (NeRFRenderer.run, shading='lambertian', shading_backward=True).
+ * sf_ngp_render_shaded_forward_train: sf_ngp_render_shaded_forward's launches, checks and outputs (same bits; no xyz_s), which also
+ * keep per sorted sample the un-normalised finite-difference gradient grad_s [N,2T,3] and the weight w_s [N,2T] (both required).
+ * sf_ngp_render_shaded_backward: gradients of the field parameters (ADDED to g's buffers, as sf_ngp_render_backward; g_embeddings
+ * NULL = table frozen) from grad_image [N,3], grad_weights_sum [N] or NULL and grad_orient [N] or NULL (d loss / d orient):
+ * the albedo takes d(col) * lambertian, the density of every sample its compositing gradient on the shaded colour (the weights
+ * inside orient are detached, as in the reference) and the six offset densities the gradient through
+ * normal = g / sqrt(max(g . g, 1e-20)), g = 0.5 (s+ - s-) / epsilon.  A sample whose g has a non-finite component passes nothing
+ * through its normal (torch would write NaN into every parameter).  light_d, the rays and the normal image get no gradient.
+ * normal_s / rgb_shaded_s / grad_s / w_s and the sorted ray are the forward's; light_d: 3 floats ON THE DEVICE.  Seven field-backward
+ * and scatter stages into one set of fixed-point sums: deterministic.  With ambient_ratio == 1 and grad_orient NULL the six offset
+ * passes are skipped: their upstream is exactly zero for finite upstream gradients (a non-finite grad_image would have put NaN = 0 * inf
+ * there; skipped, it contributes nothing through the normals and stays visible through the centre pass).  SF_ERR_INVALID before any launch: a NULL required pointer,
+ * T outside [4, 64], epsilon not finite or <= 0, ambient_ratio not finite, workspace below
+ * sf_ngp_render_shaded_backward_workspace_bytes(N, T).  N == 0: SF_OK, no launch. */
+int sf_ngp_render_shaded_forward_train(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
+                                       uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
+                                       const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
+                                       float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
+                                       float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* grad_s,
+                                       float* w_s, float* image, float* normal_image, float* orient, float* depth,
+                                       float* weights_sum, float* workspace, uint64_t workspace_bytes, void* stream);
+int sf_ngp_render_shaded_backward(const sf_ngp_field* f, const sf_ngp_field_grad* g, const float* rays_o, const float* rays_d,
+                                  const float* aabb, uint32_t N, uint32_t T, const float* nears, const float* fars,
+                                  const float* z_sorted, const float* sigma_s, const float* rgb_s, const float* normal_s,
+                                  const float* rgb_shaded_s, const float* grad_s, const float* w_s, const float* light_d,
+                                  float ambient_ratio, float epsilon, float bg_color, const float* grad_image,
+                                  const float* grad_weights_sum, const float* grad_orient, uint32_t rays_per_row,
+                                  float* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t sf_ngp_render_shaded_backward_workspace_bytes(uint32_t N, uint32_t T);
+/* DIAGNOSTIC / TEST ENTRY, outside the documented drop-in surface: it exists so that the per-stage parity tests can run and check one
+ * pass of sf_ngp_render_shaded_backward alone; the renderer never calls it and integrations should not depend on it.
+ * One of the six offset passes of sf_ngp_render_shaded_backward on its own: ADDS to g's buffers the gradient of
+ * sum_p ds_e[p] * sigma(offset point e of sorted sample p), e = 1 .. 6 (+x, -x, +y, -y, +z, -z by epsilon, clamped to the bound as
+ * sf_ngp_point_attrs offsets them); ds_e [N,2T].  Workspace: sf_ngp_render_workspace_bytes(N, T); d(features) of the pass stays at its
+ * floats [4M, 36M), level-major, M = N * 2T.  SF_ERR_INVALID before any launch as sf_ngp_render_shaded_backward, and for e outside [1, 6]. */
+int sf_ngp_render_offset_backward(const sf_ngp_field* f, const sf_ngp_field_grad* g, const float* rays_o, const float* rays_d,
+                                  const float* aabb, uint32_t N, uint32_t T, const float* z_sorted, const float* ds_e, uint32_t e,
+                                  float epsilon, uint32_t rays_per_row, float* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Fused evaluation render through the occupancy grid (`cuda_ray=True`, eval mode): replaces the host loop
  * `while step < max_steps: march_rays -> network -> composite_rays` of external/nerf/renderer_df.py:543-584 by ONE
  * launch (one ray per lane walks to the end).  `grid` = the density bitfield, C cascades of H^3 cells;

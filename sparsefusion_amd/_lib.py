@@ -123,6 +123,16 @@ SIGNATURES = {
                                                c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                                c_f32p, u64, C.c_void_p]),
     "sf_ngp_render_shaded_workspace_bytes": (u64, [u32, u32]),
+    "sf_ngp_render_shaded_forward_train": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, u32, u32, C.c_float, c_f32p, c_f32p,
+                                                     c_f32p, u32, C.c_float, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p,
+                                                     c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                     c_f32p, c_f32p, u64, C.c_void_p]),
+    "sf_ngp_render_shaded_backward": (C.c_int, [C.POINTER(SfNgpField), C.POINTER(SfNgpFieldGrad), c_f32p, c_f32p, c_f32p, u32, u32,
+                                                c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                C.c_float, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, u32, c_f32p, u64, C.c_void_p]),
+    "sf_ngp_render_shaded_backward_workspace_bytes": (u64, [u32, u32]),
+    "sf_ngp_render_offset_backward": (C.c_int, [C.POINTER(SfNgpField), C.POINTER(SfNgpFieldGrad), c_f32p, c_f32p, c_f32p, u32, u32, c_f32p,
+                                                c_f32p, u32, C.c_float, u32, c_f32p, u64, C.c_void_p]),
     "sf_ngp_render_occ_eval": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_float, u32, u32, u32,
                                          c_f32p, C.c_float, u32, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "sf_ngp_render_occ_eval_shaded": (C.c_int, [C.POINTER(SfNgpField), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_float, u32, u32,

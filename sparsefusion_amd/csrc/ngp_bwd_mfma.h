@@ -17,6 +17,7 @@
 #pragma once
 #include "sf_dev.h"
 #include "ngp_device.h"
+#include "ngp_point_attrs.h"                       // ngp_offset_point
 
 #define FB_PTS 32
 #define FB_SF 33                                   // feat row stride (floats)
@@ -48,9 +49,17 @@ struct FBArgs {
   // recompute.  feat_c / feat_f: [N * T][32] of the coarse / fine samples in sampling order, perm: [N][2T] sorted position ->
   // index in cat([coarse, fine]); all indexed with the WHOLE set's point index p_off + p.
   const float* feat_c; const float* feat_f; const uint32_t* perm;
+  // the offset instantiation only (k_ngp_field_bwd_mfma_t<1>): offset point off_e = 1 .. 6 of every sample, step off_eps (ngp_point_attrs.h)
+  uint32_t off_e; float off_eps;
 };
 
-SF_KERNEL(256) void k_ngp_field_bwd_mfma(FBArgs a) {
+// OFF = 0 (k_ngp_field_bwd_mfma): the sample points of the ray -- the albedo backward, and the centre pass of the shaded backward.
+// OFF = 1: offset point a.off_e of every sample with step a.off_eps -- the six finite-difference passes of the shaded backward
+// (ngp_shade_bwd.h): a.dsig is d(sigma) at the OFFSET points, d(albedo) is a compile-time zero (a.drgb is never read), and there is
+// no field cache.  The kernel itself is the template (a body inlined into two kernels reads the argument struct through a copy, and
+// hipcc then compiles OFF = 0 to other code than it always was).
+template <int OFF>
+SF_KERNEL(256) void k_ngp_field_bwd_mfma_t(FBArgs a) {
   SF_DYN_LDS(lds_raw);
   float* W = reinterpret_cast<float*>(lds_raw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -96,9 +105,13 @@ SF_KERNEL(256) void k_ngp_field_bwd_mfma(FBArgs a) {
       const float o[3] = {a.rays_o[n * 3], a.rays_o[n * 3 + 1], a.rays_o[n * 3 + 2]};
       const float d[3] = {a.rays_d[n * 3], a.rays_d[n * 3 + 1], a.rays_d[n * 3 + 2]};
       ngp_point(o, d, a.z_s[p], box, x);
+      if (OFF) {
+        const float xc[3] = {x[0], x[1], x[2]};
+        ngp_offset_point(xc, (int)a.off_e, a.off_eps, a.bound, x);
+      }
       inside = ngp_unit(x, a.bound, x01);
     }
-    if (a.feat_c) {
+    if (!OFF && a.feat_c) {
       // cached features: this lane's 16 floats (levels half*8 .. half*8+7) of the sample's row
       f32x4 fv[4];
 #pragma unroll
@@ -205,9 +218,11 @@ SF_KERNEL(256) void k_ngp_field_bwd_mfma(FBArgs a) {
         if (half == 0) {
           const float pre = o0 + ngp_blob(x);
           d0 = a.dsig[p] * expf(fminf(fmaxf(pre, -15.0f), 15.0f));            // trunc_exp backward
-          const float sg = ngp_sigmoid(o1);
-          d1 = a.drgb[p * 3 + 0] * sg * (1.0f - sg);
-        } else {
+          if (!OFF) {
+            const float sg = ngp_sigmoid(o1);
+            d1 = a.drgb[p * 3 + 0] * sg * (1.0f - sg);
+          }
+        } else if (!OFF) {
           const float s0 = ngp_sigmoid(o0), s1 = ngp_sigmoid(o1);
           d0 = a.drgb[p * 3 + 1] * s0 * (1.0f - s0);
           d1 = a.drgb[p * 3 + 2] * s1 * (1.0f - s1);
@@ -373,3 +388,7 @@ SF_KERNEL(256) void k_ngp_field_bwd_mfma(FBArgs a) {
   sf_grad_add(a.g_b1 + lane, a.f_b1 + lane, accb1, a.thr);
   sf_grad_add(a.g_b0 + lane, a.f_b0 + lane, accb0, a.thr);
 }
+
+#ifdef SF_HOST_EMU
+static inline void k_ngp_field_bwd_mfma(FBArgs a) { k_ngp_field_bwd_mfma_t<0>(a); }      // the name the harnesses of tests/hostemu call
+#endif

@@ -21,6 +21,16 @@ struct NgpPointAttrs { float sigma; float albedo[3]; float grad[3]; float normal
 // torch.clamp(v, -b, b): NaN propagates (fminf / fmaxf alone would return the bound)
 SF_HD float ngp_clamp_sym(float v, float b) { return (v != v) ? v : fminf(fmaxf(v, -b), b); }
 
+// Offset point e = 1 .. 6 of x (the rule in the header comment).  One function for the forward (ngp_point_attrs below) and for the
+// offset instantiations of the backward kernels (ngp_bwd_mfma.h, ngp_scatter_bin.h, ngp_render.hip): the backward's point is the
+// forward's fp32 point bit for bit.
+SF_HD void ngp_offset_point(const float x[3], int e, float eps, float bound, float xe[3]) {
+  const int axis = (e - 1) >> 1;
+  const float o = (e & 1) ? eps : -eps;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) xe[d] = ngp_clamp_sym(SF_ADD(x[d], d == axis ? o : 0.0f), bound);
+}
+
 // The finite-difference arithmetic, shared by ngp_point_attrs below and the eight-lanes-per-ray shaded render (ngp_occ_shade.h),
 // whose normals are therefore the same bits: one component of the gradient from the sigmas at x + eps e_a and x - eps e_a ...
 SF_HD float ngp_fd_grad(float sp, float sn, float eps) { return SF_DIV(SF_MUL(0.5f, SF_SUB(sp, sn)), eps); }
@@ -50,10 +60,8 @@ SF_HD void ngp_point_attrs(const NgpLevels& lv, const float* __restrict__ table,
     // keeps the loop-invariant weight reads (LDS on the GPU) inside the loop: hoisted, they would be pinned in registers and spill
     asm volatile("" ::: "memory");
     const int axis = (e - 1) >> 1;                     // -1 for the centre
-    const float o = (e & 1) ? eps : -eps;
-    float xe[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) xe[d] = e == 0 ? x[d] : ngp_clamp_sym(SF_ADD(x[d], d == axis ? o : 0.0f), bound);
+    float xe[3] = {x[0], x[1], x[2]};
+    if (e != 0) ngp_offset_point(x, e, eps, bound, xe);
     float x01[3], feat[NGP_FEAT], h1[NGP_HID], h2[NGP_HID], out[NGP_OUT];
     const bool inside = ngp_unit(xe, bound, x01);
     ngp_encode(lv, table, x01, inside, feat);

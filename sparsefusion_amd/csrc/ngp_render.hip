@@ -29,6 +29,7 @@
 #include "ngp_composite_wave.h"
 #include "ngp_scatter_bin.h"
 #include "ngp_shade.h"
+#include "ngp_shade_bwd.h"
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
@@ -123,12 +124,14 @@ __global__ __launch_bounds__(64) void k_ngp_sample_fine(
 // NT threads share one 80 KB LDS cache (4096 slots of 64-bit fixed-point sums; r02: 8192 of floats) (one workgroup per CU): NT = 1024 puts 4 waves on every SIMD -- the loop body is a
 // chain of dependent global loads, hash arithmetic and LDS atomics, and with the first version's 256 threads (ONE wave per
 // SIMD) every one of those latencies was exposed.  `last_level`: levels [0, last_level) are walked by this kernel.
-template <int NT>
+// OFF = 1 (here and in k_ngp_scatter_fine): the points are offset point `off_e` (1 .. 6, ngp_point_attrs.h) of every sample, step
+// `off_eps` -- the finite-difference passes of the shaded backward.  OFF = 0 ignores both.
+template <int NT, int OFF = 0>
 __global__ __launch_bounds__(NT) void k_ngp_scatter(
     NgpLevels lv, float bound, long long* __restrict__ gtable, float* __restrict__ gtable_f, float thr, const float* __restrict__ rays_o,
     const float* __restrict__ rays_d, const float* __restrict__ aabb, const float* __restrict__ z_s,
     const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t rays_per_row, uint32_t cached_levels,
-    uint32_t last_level, uint32_t sc_run) {
+    uint32_t last_level, uint32_t sc_run, uint32_t off_e, float off_eps) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   uint32_t* tags = reinterpret_cast<uint32_t*>(smem);            // [SC_SLOTS]
   long long* vals = reinterpret_cast<long long*>(smem + SC_SLOTS);   // [SC_SLOTS][2], fixed point (sf_dev.h): exact, order-independent sums
@@ -193,6 +196,10 @@ __global__ __launch_bounds__(NT) void k_ngp_scatter(
         if (dfc == 0.0f) continue;                               // outside points / dead samples contribute nothing
         float x[3], x01[3];
         ngp_point(o, d, z_s[p], box, x);
+        if (OFF) {
+          const float xc[3] = {x[0], x[1], x[2]};
+          ngp_offset_point(xc, (int)off_e, off_eps, bound, x);
+        }
         if (!ngp_unit(x, bound, x01)) continue;
         NgpCell c;
         ngp_cell(lv, l, x01, c);
@@ -235,10 +242,12 @@ __global__ __launch_bounds__(NT) void k_ngp_scatter(
 // Fine levels (cell smaller than the patch footprint: nothing to merge in LDS): no LDS frame, so 8 waves per SIMD hide the
 // latency of the loads in front of every atomic.  Work item = (level, sample) in level-major order (the dfeat layout),
 // lane quads as above: 16 contiguous bytes per atomic instruction and quad.
+template <int OFF>
 __global__ __launch_bounds__(256) void k_ngp_scatter_fine(
     NgpLevels lv, float bound, long long* __restrict__ gtable, float* __restrict__ gtable_f, float thr, const float* __restrict__ rays_o,
     const float* __restrict__ rays_d, const float* __restrict__ aabb, const float* __restrict__ z_s,
-    const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t first_level, uint32_t P_stride, uint32_t p_off) {
+    const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t first_level, uint32_t P_stride, uint32_t p_off, uint32_t off_e,
+    float off_eps) {
   // this launch walks the N rays behind the (pre-offset) ray / sample pointers = points [p_off, p_off + N * T2) of a set of
   // P_stride points, whose level-major layout dfeat keeps
   const uint32_t P = N * T2;
@@ -257,6 +266,10 @@ __global__ __launch_bounds__(256) void k_ngp_scatter_fine(
     const float d[3] = {rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2]};
     float x[3], x01[3];
     ngp_point(o, d, z_s[p], box, x);
+    if (OFF) {
+      const float xc[3] = {x[0], x[1], x[2]};
+      ngp_offset_point(xc, (int)off_e, off_eps, bound, x);
+    }
     if (!ngp_unit(x, bound, x01)) continue;
     NgpCell c;
     ngp_cell(lv, l, x01, c);
@@ -432,14 +445,15 @@ extern "C" uint64_t sf_ngp_render_shaded_workspace_bytes(uint32_t N, uint32_t T)
 
 // Shaded render without gradient (ngp_shade.h).  The albedo forward runs first and unchanged: sample_pdf needs the coarse sigmas
 // before any normal can be placed, and it leaves the sorted ray the two kernels below work on.  Every check comes before the
-// first launch.
-extern "C" int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
-                                            uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
-                                            const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
-                                            float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
-                                            float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* xyz_s,
-                                            float* image, float* normal_image, float* orient, float* depth, float* weights_sum,
-                                            float* workspace, uint64_t workspace_bytes, void* stream) {
+// first launch.  grad_s / w_s (both or none): what the backward needs per sorted sample next to the other outputs
+// (sf_ngp_render_shaded_forward_train); every other output is the same bits with or without them.
+static int ngp_render_shaded_forward_body(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
+                                          uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
+                                          const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
+                                          float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
+                                          float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* xyz_s,
+                                          float* grad_s, float* w_s, float* image, float* normal_image, float* orient, float* depth,
+                                          float* weights_sum, float* workspace, uint64_t workspace_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!light_d) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: null light_d");
   if (!isfinite(epsilon) || !(epsilon > 0.0f)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded: epsilon must be finite and > 0");
@@ -462,15 +476,42 @@ extern "C" int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* 
   s.f = field_ptrs(f); s.lv = lv;
   s.rays_o = rays_o; s.rays_d = rays_d; s.aabb = aabb; s.z_s = z_sorted; s.rgb_s = rgb_s; s.light_d = light_d;
   s.P = P; s.T2 = 2 * T; s.ratio = ambient_ratio; s.eps = epsilon;
-  s.normal_s = normal_s; s.rgb_shaded_s = rgb_shaded_s; s.xyz_s = xyz_s;
+  s.normal_s = normal_s; s.rgb_shaded_s = rgb_shaded_s; s.xyz_s = xyz_s; s.grad_s = grad_s;
   k_ngp_shade<<<sf_grid_cap(sf_div_up(P, 256)), 256, 0, st>>>(s);
   SF_CHECK_LAUNCH("ngp_shade");
   // image, depth and weights_sum are written again: the same scan on the same sorted ray (depth and weights_sum come out bit for bit)
   k_ngp_composite_sorted_wave<<<sf_div_up(N, 4), 256, 0, st>>>(
       CompositeSortedArgs{z_sorted, sigma_s, rgb_shaded_s, normal_s, rays_d, nears, fars, N, T, bg_color, image, depth, weights_sum,
-                          normal_image, orient});
+                          normal_image, orient, w_s});
   SF_CHECK_LAUNCH("ngp_composite_sorted");
   return SF_OK;
+}
+
+extern "C" int sf_ngp_render_shaded_forward(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
+                                            uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
+                                            const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
+                                            float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
+                                            float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* xyz_s,
+                                            float* image, float* normal_image, float* orient, float* depth, float* weights_sum,
+                                            float* workspace, uint64_t workspace_bytes, void* stream) {
+  return ngp_render_shaded_forward_body(f, rays_o, rays_d, aabb, N, T, min_near, lin, u_coarse, u_fine, u_fine_row_stride, bg_color, light_d,
+                                        ambient_ratio, epsilon, nears, fars, z_sorted, sigma_s, rgb_s, normal_s, rgb_shaded_s, xyz_s, nullptr,
+                                        nullptr, image, normal_image, orient, depth, weights_sum, workspace, workspace_bytes, stream);
+}
+
+// The shaded forward of a render that will be differentiated (sf_ngp_render_shaded_backward): the same launches, which also keep the
+// un-normalised gradient grad_s [N,2T,3] and the weights w_s [N,2T] of every sorted sample.
+extern "C" int sf_ngp_render_shaded_forward_train(const sf_ngp_field* f, const float* rays_o, const float* rays_d, const float* aabb,
+                                                  uint32_t N, uint32_t T, float min_near, const float* lin, const float* u_coarse,
+                                                  const float* u_fine, uint32_t u_fine_row_stride, float bg_color, const float* light_d,
+                                                  float ambient_ratio, float epsilon, float* nears, float* fars, float* z_sorted,
+                                                  float* sigma_s, float* rgb_s, float* normal_s, float* rgb_shaded_s, float* grad_s,
+                                                  float* w_s, float* image, float* normal_image, float* orient, float* depth,
+                                                  float* weights_sum, float* workspace, uint64_t workspace_bytes, void* stream) {
+  if (!grad_s || !w_s) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_forward_train: null grad_s / w_s");
+  return ngp_render_shaded_forward_body(f, rays_o, rays_d, aabb, N, T, min_near, lin, u_coarse, u_fine, u_fine_row_stride, bg_color, light_d,
+                                        ambient_ratio, epsilon, nears, fars, z_sorted, sigma_s, rgb_s, normal_s, rgb_shaded_s, nullptr, grad_s,
+                                        w_s, image, normal_image, orient, depth, weights_sum, workspace, workspace_bytes, stream);
 }
 
 
@@ -481,9 +522,11 @@ static constexpr size_t FB_LDS_BYTES = (size_t)FB_LDS_FLOATS * sizeof(float);
 static constexpr size_t SC_LDS_BYTES = (size_t)SC_SLOTS * (sizeof(uint32_t) + 2 * sizeof(long long));
 
 static int ngp_bwd_raise_lds_limits() {             // raised dynamic-LDS limits are per-device function attributes
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma_t<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess)
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma_t<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess)
     SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot raise the dynamic LDS limits");
   return SF_OK;
 }
@@ -561,6 +604,11 @@ struct SideJoin {
   ~SideJoin() { (void)join(); }
 };
 
+static int ngp_bwd_field_scatter(const sf_ngp_field* f, const sf_ngp_field_grad* g, const NgpLevels& lv, const float* rays_o,
+                                 const float* rays_d, const float* aabb, uint32_t N, uint32_t T, const float* z_sorted, uint32_t rays_per_row,
+                                 const float* field_cache, float* workspace, const float* ds_off, uint32_t e_begin, uint32_t e_end, float eps,
+                                 hipStream_t st);
+
 extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_grad* g, const float* rays_o,
                                       const float* rays_d, const float* aabb, uint32_t N, uint32_t T,
                                       const float* nears, const float* fars, const float* z_sorted,
@@ -575,7 +623,28 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   NgpLevels lv;
   if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
   const uint64_t M = (uint64_t)N * 2 * T;
+  float* dsig = workspace;
+  float* drgb = dsig + M;
+
+  // wave-per-ray backward: the forward's scans run in reverse (suffix sums in double)
+  k_ngp_composite_bwd_wave<<<sf_div_up(N, 4), 256, 0, st>>>(
+      CompositeBwdArgs{z_sorted, sigma_s, rgb_s, nears, fars, N, T, bg_color, grad_image, grad_weights_sum, dsig, drgb});
+  SF_CHECK_LAUNCH("ngp_composite_bwd");
+  return ngp_bwd_field_scatter(f, g, lv, rays_o, rays_d, aabb, N, T, z_sorted, rays_per_row, field_cache, workspace, nullptr, 0, 1, 0.0f, st);
+}
+
+// Everything of a render backward behind the composite backward: the field backward and the table-gradient scatter of the sorted samples,
+// with d(sigma) [M] | d(albedo) [3M] at the head of `workspace` (the layout of ngp_bwd_plan.h), summed in fixed point and converted into
+// g's buffers.  Passes e = e_begin .. e_end - 1: pass 0 is the samples themselves (the albedo backward, sf_ngp_render_backward, is [0, 1)),
+// pass e = 1 .. 6 their offset points e of step `eps` with d(sigma) in plane e - max(e_begin, 1) of ds_off [.][M] (ngp_shade_bwd.h; the
+// OFF = 1 instantiations: d(albedo) = 0).  All passes add into the SAME accumulators, converted once; d(feat) is one pass wide and reused.
+static int ngp_bwd_field_scatter(const sf_ngp_field* f, const sf_ngp_field_grad* g, const NgpLevels& lv, const float* rays_o,
+                                 const float* rays_d, const float* aabb, uint32_t N, uint32_t T, const float* z_sorted, uint32_t rays_per_row,
+                                 const float* field_cache, float* workspace, const float* ds_off, uint32_t e_begin, uint32_t e_end, float eps,
+                                 hipStream_t st) {
+  const uint64_t M = (uint64_t)N * 2 * T;
   const uint32_t T2 = 2 * T;
+  const uint32_t passes = e_end - e_begin, plane0 = e_begin ? e_begin : 1;
   float* dsig = workspace;
   float* drgb = dsig + M;
   float* dfeat = g->g_embeddings ? drgb + 3 * M : nullptr;        // NULL table gradient = table frozen
@@ -585,15 +654,10 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
   const NgpScatterPlan sp = ngp_scatter_plan(lv, dfeat != nullptr, N, T);
   const bool per_chunk = dfeat && sp.last < lv.L;                 // levels [last, L) are scattered chunk by chunk
   const NgpChunks plan = per_chunk ? ngp_bwd_plan(N) : ngp_bwd_one_chunk(N);
-  const float thr_mlp = ngp_bwd_thr_mlp(plan.n);
+  const float thr_mlp = ngp_bwd_thr_mlp(plan.n * passes);       // (every pass adds its per-chunk addends to the same sums)
   // a fixed-point sum receives at most 8 addends per sample (the 8 corners of a cell, hash collisions included): thresholds per
   // sf_dev.h keep every table sum below 2^18; larger addends take the fp32 atomics (sf_grad_add)
-  const float thr_tab = sf_fix_thr(8.0 * (double)M);
-
-  // wave-per-ray backward: the forward's scans run in reverse (suffix sums in double)
-  k_ngp_composite_bwd_wave<<<sf_div_up(N, 4), 256, 0, st>>>(
-      CompositeBwdArgs{z_sorted, sigma_s, rgb_s, nears, fars, N, T, bg_color, grad_image, grad_weights_sum, dsig, drgb});
-  SF_CHECK_LAUNCH("ngp_composite_bwd");
+  const float thr_tab = sf_fix_thr(8.0 * (double)passes * (double)M);
 
   int dev_id = 0;
   if (hipGetDevice(&dev_id) != hipSuccess) SF_FAIL(SF_ERR_LAUNCH, "hipGetDevice failed");
@@ -652,42 +716,53 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
     side_lk.lock();
     side_join.dev = dev; side_join.st = st;
   }
-  for (uint32_t c = 0; c < plan.n; ++c) {
-    const uint32_t n0 = plan.start[c], Nc = plan.start[c + 1] - n0;
-    const uint32_t Pc = Nc * T2, P0 = n0 * T2;
-    // matrix-core field backward of chunk c: one wave per 32 points and trip, six fp32 GEMMs on v_mfma_f32_16x16x4_f32 (ngp_bwd_mfma.h)
-    a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3;
-    a.z_s = z_sorted + (size_t)P0; a.dsig = dsig + (size_t)P0; a.drgb = drgb + (size_t)P0 * 3;
-    a.P = Pc; a.p_off = P0;
-    const uint32_t grid = ngp_field_bwd_grid(Pc, FB_PTS);
-    // with a field cache: k_ngp_field_bwd_pipe (ngp_bwd_pipe.h; same trips, same LDS image, same values) unless switched off
-    const int pipe = field_cache && g_field_bwd_pipe.load(std::memory_order_relaxed) != 0 ? 1 : 0;
-    if (pipe) k_ngp_field_bwd_pipe<<<grid, 256, FB_LDS_BYTES, st>>>(a);
-    else k_ngp_field_bwd_mfma<<<grid, 256, FB_LDS_BYTES, st>>>(a);
-    SF_CHECK_LAUNCH(pipe ? "ngp_field_bwd_pipe" : "ngp_field_bwd_mfma");
-    g_field_bwd_launches[pipe].fetch_add(1, std::memory_order_relaxed);
-    if (!per_chunk) continue;
-    if (fork && side_join.fork()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: fork failed");
-    hipStream_t sf = fork ? dev->side : st;
-    if (sp.binned) {
-      b.rays_o = a.rays_o; b.rays_d = a.rays_d; b.z_s = a.z_s; b.P = Pc; b.p_off = P0;
-      const uint32_t tiles = sf_div_up(Pc, SB_THREADS);
-      k_ngp_bin<<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
-      SF_CHECK_LAUNCH("ngp_bin");
-      k_ngp_bin_reduce<<<sp.total_buckets, SBR_THREADS, 0, sf>>>(r);         // leaves the cursors at zero for the next chunk
-      SF_CHECK_LAUNCH("ngp_bin_reduce");
-    } else {
-      const uint64_t items = (uint64_t)4 * Pc * (lv.L - sp.last);
-      const uint32_t grid_f = (uint32_t)(items / 256 < 16384 ? (items + 255) / 256 : 16384);
-      k_ngp_scatter_fine<<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, sp.last,
-                                                 (uint32_t)M, P0);
-      SF_CHECK_LAUNCH("ngp_scatter_fine");
+  // pass 0: the samples themselves; passes e = 1 .. 6 (the shaded backward): their offset points e
+  for (uint32_t e = e_begin; e < e_end; ++e) {
+    a.off_e = e; a.off_eps = eps; b.off_e = e; b.off_eps = eps;
+    for (uint32_t c = 0; c < plan.n; ++c) {
+      const uint32_t n0 = plan.start[c], Nc = plan.start[c + 1] - n0;
+      const uint32_t Pc = Nc * T2, P0 = n0 * T2;
+      // matrix-core field backward of chunk c: one wave per 32 points and trip, six fp32 GEMMs on v_mfma_f32_16x16x4_f32 (ngp_bwd_mfma.h)
+      a.rays_o = rays_o + (size_t)n0 * 3; a.rays_d = rays_d + (size_t)n0 * 3;
+      a.z_s = z_sorted + (size_t)P0; a.dsig = (e ? ds_off + (size_t)(e - plane0) * M : dsig) + (size_t)P0; a.drgb = drgb + (size_t)P0 * 3;
+      a.P = Pc; a.p_off = P0;
+      const uint32_t grid = ngp_field_bwd_grid(Pc, FB_PTS);
+      // with a field cache: k_ngp_field_bwd_pipe (ngp_bwd_pipe.h; same trips, same LDS image, same values) unless switched off
+      const int pipe = field_cache && g_field_bwd_pipe.load(std::memory_order_relaxed) != 0 ? 1 : 0;
+      if (e) k_ngp_field_bwd_mfma_t<1><<<grid, 256, FB_LDS_BYTES, st>>>(a);
+      else if (pipe) k_ngp_field_bwd_pipe<<<grid, 256, FB_LDS_BYTES, st>>>(a);
+      else k_ngp_field_bwd_mfma_t<0><<<grid, 256, FB_LDS_BYTES, st>>>(a);
+      SF_CHECK_LAUNCH(e ? "ngp_field_bwd_mfma_off" : pipe ? "ngp_field_bwd_pipe" : "ngp_field_bwd_mfma");
+      if (!e) g_field_bwd_launches[pipe].fetch_add(1, std::memory_order_relaxed);
+      if (!per_chunk) continue;
+      if (fork && side_join.fork()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: fork failed");
+      hipStream_t sf = fork ? dev->side : st;
+      if (sp.binned) {
+        b.rays_o = a.rays_o; b.rays_d = a.rays_d; b.z_s = a.z_s; b.P = Pc; b.p_off = P0;
+        const uint32_t tiles = sf_div_up(Pc, SB_THREADS);
+        if (e) k_ngp_bin_t<1><<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
+        else k_ngp_bin_t<0><<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
+        SF_CHECK_LAUNCH("ngp_bin");
+        k_ngp_bin_reduce<<<sp.total_buckets, SBR_THREADS, 0, sf>>>(r);         // leaves the cursors at zero for the next chunk
+        SF_CHECK_LAUNCH("ngp_bin_reduce");
+      } else {
+        const uint64_t items = (uint64_t)4 * Pc * (lv.L - sp.last);
+        const uint32_t grid_f = (uint32_t)(items / 256 < 16384 ? (items + 255) / 256 : 16384);
+        if (e) k_ngp_scatter_fine<1><<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2,
+                                                              sp.last, (uint32_t)M, P0, e, eps);
+        else k_ngp_scatter_fine<0><<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, sp.last,
+                                                      (uint32_t)M, P0, 0u, 0.0f);
+        SF_CHECK_LAUNCH("ngp_scatter_fine");
+      }
     }
-  }
-  if (dfeat && sp.last > 0) {
-    const uint32_t grid_sc = sf_div_up(N, SC_RAYS);
-    k_ngp_scatter<1024><<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN);
-    SF_CHECK_LAUNCH("ngp_scatter");
+    if (dfeat && sp.last > 0) {
+      const uint32_t grid_sc = sf_div_up(N, SC_RAYS);
+      if (e) k_ngp_scatter<1024, 1><<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN, e, eps);
+      else k_ngp_scatter<1024><<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN, 0u, 0.0f);
+      SF_CHECK_LAUNCH("ngp_scatter");
+    }
+    // the next pass rewrites d(feat): the side stream's last bin / scatter of this pass must have read it
+    if (e + 1 < e_end && side_join.join()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: join failed");
   }
   if (side_join.join()) SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: join failed");
   {
@@ -697,4 +772,72 @@ extern "C" int sf_ngp_render_backward(const sf_ngp_field* f, const sf_ngp_field_
     SF_CHECK_LAUNCH("fix_to_f32");
   }
   return SF_OK;                                    // (fix frees the accumulators on the stream, behind the conversion)
+}
+
+// ---------------------------------------------------------------------------
+// backward of the shaded render (ngp_shade_bwd.h): albedo, and the density through the finite-difference normal
+// ---------------------------------------------------------------------------
+extern "C" uint64_t sf_ngp_render_shaded_backward_workspace_bytes(uint32_t N, uint32_t T) {
+  return ngp_render_workspace_bytes(N, T) + (uint64_t)6 * N * 2 * T * sizeof(float);      // the albedo backward's, then ds_off [6][N * 2T]
+}
+
+// 1. k_ngp_composite_bwd_wave on the SHADED colour: d(sigma) of the centres (the weights inside the orientation term are detached, so
+//    grad_orient adds nothing here) and d(col);  2. k_ngp_shade_bwd: d(albedo) over d(col), d(sigma) at the six offset points;
+// 3. the field backward + scatter stage seven times into one set of accumulators (ngp_bwd_field_scatter).  With ambient_ratio == 1 and no
+// grad_orient the upstream of the six offset passes is exactly zero and they are skipped -- stricter than running them in one case: a
+// non-finite d(col) would make k_ngp_shade_bwd write NaN (0 * inf) into ds_off, which the skip does not carry into the offset passes
+// (the centre pass still carries it: d(albedo) = d(col) lam).  Every check comes before the first launch.
+extern "C" int sf_ngp_render_shaded_backward(const sf_ngp_field* f, const sf_ngp_field_grad* g, const float* rays_o, const float* rays_d,
+                                             const float* aabb, uint32_t N, uint32_t T, const float* nears, const float* fars,
+                                             const float* z_sorted, const float* sigma_s, const float* rgb_s, const float* normal_s,
+                                             const float* rgb_shaded_s, const float* grad_s, const float* w_s, const float* light_d,
+                                             float ambient_ratio, float epsilon, float bg_color, const float* grad_image,
+                                             const float* grad_weights_sum, const float* grad_orient, uint32_t rays_per_row,
+                                             float* workspace, uint64_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!f || !g || !rays_o || !rays_d || !aabb || !nears || !fars || !z_sorted || !sigma_s || !rgb_s || !normal_s || !rgb_shaded_s || !grad_s ||
+      !w_s || !light_d || !grad_image)
+    SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_backward: null pointer");
+  if (!isfinite(epsilon) || !(epsilon > 0.0f)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_backward: epsilon must be finite and > 0");
+  if (!isfinite(ambient_ratio)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_backward: ambient_ratio must be finite");
+  if (N == 0) return SF_OK;
+  if (T < 4 || T > 64) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_backward: T must be in [4,64]");
+  if ((uint64_t)N * 2 * T >= (1ull << 32)) SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_backward: N * 2T must be below 2^32");
+  if (!workspace || workspace_bytes < sf_ngp_render_shaded_backward_workspace_bytes(N, T))
+    SF_FAIL(SF_ERR_INVALID, "ngp_render_shaded_backward: workspace too small");
+  NgpLevels lv;
+  if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
+  const uint64_t M = (uint64_t)N * 2 * T;
+  float* dsig = workspace;
+  float* dcol = dsig + M;                                          // d(col), overwritten in place by d(albedo)
+  float* ds_off = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ngp_render_workspace_bytes(N, T));
+  const bool offsets = ambient_ratio != 1.0f || grad_orient != nullptr;
+  k_ngp_composite_bwd_wave<<<sf_div_up(N, 4), 256, 0, st>>>(
+      CompositeBwdArgs{z_sorted, sigma_s, rgb_shaded_s, nears, fars, N, T, bg_color, grad_image, grad_weights_sum, dsig, dcol});
+  SF_CHECK_LAUNCH("ngp_composite_bwd");
+  ShadeBwdArgs sb{};
+  sb.dcol = dcol; sb.rgb_s = rgb_s; sb.normal_s = normal_s; sb.grad_s = grad_s; sb.w_s = w_s; sb.rays_d = rays_d; sb.light_d = light_d;
+  sb.g_orient = grad_orient; sb.P = (uint32_t)M; sb.T2 = 2 * T; sb.ratio = ambient_ratio; sb.eps = epsilon; sb.dalb = dcol; sb.ds_off = ds_off;
+  k_ngp_shade_bwd<<<sf_grid_cap(sf_div_up((uint32_t)M, 256)), 256, 0, st>>>(sb);
+  SF_CHECK_LAUNCH("ngp_shade_bwd");
+  return ngp_bwd_field_scatter(f, g, lv, rays_o, rays_d, aabb, N, T, z_sorted, rays_per_row, nullptr, workspace, ds_off, 0, offsets ? 7 : 1, epsilon, st);
+}
+
+// ONE offset pass on its own: adds to g's buffers the gradient of sum_p ds_e[p] sigma(offset point e of sorted sample p), e = 1 .. 6 -- the
+// stage sf_ngp_render_shaded_backward runs six times, for callers (and tests) that hold d(sigma) at one offset.  Workspace as
+// sf_ngp_render_backward's; d(feat) of the pass is left at floats [4M, 36M) of it, level-major, M = N * 2T.
+extern "C" int sf_ngp_render_offset_backward(const sf_ngp_field* f, const sf_ngp_field_grad* g, const float* rays_o, const float* rays_d,
+                                             const float* aabb, uint32_t N, uint32_t T, const float* z_sorted, const float* ds_e, uint32_t e,
+                                             float epsilon, uint32_t rays_per_row, float* workspace, uint64_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!f || !g || !rays_o || !rays_d || !aabb || !z_sorted || !ds_e) SF_FAIL(SF_ERR_INVALID, "ngp_render_offset_backward: null pointer");
+  if (e < 1 || e > 6) SF_FAIL(SF_ERR_INVALID, "ngp_render_offset_backward: e must be in [1,6]");
+  if (!isfinite(epsilon) || !(epsilon > 0.0f)) SF_FAIL(SF_ERR_INVALID, "ngp_render_offset_backward: epsilon must be finite and > 0");
+  if (N == 0) return SF_OK;
+  if (T < 4 || T > 64) SF_FAIL(SF_ERR_INVALID, "ngp_render_offset_backward: T must be in [4,64]");
+  if ((uint64_t)N * 2 * T >= (1ull << 32)) SF_FAIL(SF_ERR_INVALID, "ngp_render_offset_backward: N * 2T must be below 2^32");
+  if (!workspace || workspace_bytes < sf_ngp_render_workspace_bytes(N, T)) SF_FAIL(SF_ERR_INVALID, "ngp_render_offset_backward: workspace too small");
+  NgpLevels lv;
+  if (int rc = sf_ngp_make_levels(f, &lv, st)) return rc;
+  return ngp_bwd_field_scatter(f, g, lv, rays_o, rays_d, aabb, N, T, z_sorted, rays_per_row, nullptr, workspace, ds_e, e, e + 1, epsilon, st);
 }

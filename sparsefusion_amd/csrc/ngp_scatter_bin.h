@@ -23,6 +23,7 @@
 #pragma once
 #include "sf_dev.h"
 #include "ngp_device.h"
+#include "ngp_point_attrs.h"                       // ngp_offset_point
 #include "ngp_bwd_plan.h"                          // the buckets: SB_ROWS_LOG, SB_ROWS, SB_MAX_BUCKETS
 
 #define SB_THREADS 1024
@@ -47,6 +48,7 @@ struct SBArgs {
   f32x4* ent;                  // [buckets][cap] 16-byte entries {word, a, b, ratio} (sb_pack below)
   uint32_t P, T2, first_level, P_stride, p_off, cap;
   uint32_t bucket0[NGP_MAX_LEVELS + 1];      // first bucket of level l (levels below first_level hold none)
+  uint32_t off_e; float off_eps;             // k_ngp_bin_t<1> only: offset point off_e = 1 .. 6 of every sample, step off_eps (ngp_point_attrs.h)
 };
 
 // One 16-byte entry per x-corner pair.  The four contributions of a pair are the outer product (w0, w1) x (dF0, dF1): the entry keeps
@@ -72,7 +74,10 @@ SF_DEV bool sb_z_dropped(const NgpLevels& lv, uint32_t l) {
   const uint32_t step = lv.resolution[l] + 1;
   return lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
 }
-SF_KERNEL(SB_THREADS) void k_ngp_bin(SBArgs a) {
+// OFF = 0 is k_ngp_bin.  OFF = 1: the points are offset point a.off_e of every sample, step a.off_eps (the shaded backward; the kernel
+// itself is the template, as k_ngp_field_bwd_mfma_t)
+template <int OFF>
+SF_KERNEL(SB_THREADS) void k_ngp_bin_t(SBArgs a) {
   SF_SHARED uint32_t cnt[SB_G][SB_MAX_BUCKETS];
   SF_SHARED uint32_t base[SB_G][SB_MAX_BUCKETS];
   const uint32_t tid = threadIdx.x;
@@ -92,6 +97,10 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin(SBArgs a) {
       const float d[3] = {a.rays_d[n * 3], a.rays_d[n * 3 + 1], a.rays_d[n * 3 + 2]};
       float x[3];
       ngp_point(o, d, a.z_s[p], box, x);
+      if (OFF) {
+        const float xc[3] = {x[0], x[1], x[2]};
+        ngp_offset_point(xc, (int)a.off_e, a.off_eps, a.bound, x);
+      }
       inside = ngp_unit(x, a.bound, x01);
     }
     for (uint32_t l0 = a.first_level; l0 < a.lv.L; l0 += SB_G) {
@@ -167,6 +176,9 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin(SBArgs a) {
     }
   }
 }
+#ifdef SF_HOST_EMU
+static inline void k_ngp_bin(SBArgs a) { k_ngp_bin_t<0>(a); }      // the name the harnesses of tests/hostemu call
+#endif
 
 struct SBRArgs {
   NgpLevels lv;

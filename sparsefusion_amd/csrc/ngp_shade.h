@@ -26,6 +26,7 @@ struct ShadeArgs {
   uint32_t P, T2;                                                // N * 2T sorted samples, 2T
   float ratio, eps;
   float* normal_s; float* rgb_shaded_s; float* xyz_s;            // [N][2T][3] each; xyz_s or null
+  float* grad_s;                                                 // [N][2T][3] or null: the un-normalised gradient (kept for the backward, ngp_shade_bwd.h)
 };
 
 // ngp_lambertian (ambient + diffuse factor of one sample) lives in ngp_point_attrs.h, next to the normal it shades
@@ -53,6 +54,7 @@ SF_KERNEL(256) void k_ngp_shade(ShadeArgs a) {
       a.normal_s[p * 3 + c] = at.normal[c];
       a.rgb_shaded_s[p * 3 + c] = SF_MUL(a.rgb_s[p * 3 + c], lam);
       if (a.xyz_s) a.xyz_s[p * 3 + c] = x[c];
+      if (a.grad_s) a.grad_s[p * 3 + c] = at.grad[c];
     }
   }
 }
@@ -64,6 +66,7 @@ struct CompositeSortedArgs {
   float bg;
   float* image; float* depth; float* weights_sum;                                 // [N][3], [N], [N]
   float* normal_image; float* orient;                                             // or null: [N][3] sum w n, [N] sum w max(n . d, 0)^2
+  float* w_s;                                                                     // or null: [N][2T] the weights (kept for the backward)
 };
 
 SF_KERNEL(256) void k_ngp_composite_sorted_wave(CompositeSortedArgs a) {
@@ -103,6 +106,7 @@ SF_KERNEL(256) void k_ngp_composite_sorted_wave(CompositeSortedArgs a) {
   if (lane == 0) excl = 1.0;
   const float w0 = SF_MUL(a0, (float)excl);
   const float w1 = SF_MUL(a1, (float)(excl * f0));
+  if (a.w_s && live) { a.w_s[q] = w0; a.w_s[q + 1] = w1; }
   const float raw0 = SF_DIV(SF_SUB(z0, near), span), raw1 = SF_DIV(SF_SUB(z1, near), span);
   const float oz0 = (raw0 != raw0) ? raw0 : fminf(fmaxf(raw0, 0.0f), 1.0f);   // NaN (miss rays: 0/0) propagates like torch.clamp
   const float oz1 = (raw1 != raw1) ? raw1 : fminf(fmaxf(raw1, 0.0f), 1.0f);

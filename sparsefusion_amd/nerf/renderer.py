@@ -48,6 +48,7 @@ def get_default_torch_ngp_opt():
     opt.lambda_opacity = 0
     opt.lambda_orient = 1e-2
     opt.lambda_smooth = 0
+    opt.shading_backward = False      # run(shading='lambertian'): True = the differentiable shaded render (an extension, see `run`)
     return opt
 
 
@@ -149,6 +150,67 @@ class _RenderFn(torch.autograd.Function):
                                         _lib.ptr(work), wbytes, _lib.stream_ptr())
         _lib.check(rc, "ngp_render_backward")
         return (None,) * 13 + tuple(grads)
+
+
+class _ShadedRenderFn(torch.autograd.Function):
+    """The Lambertian-shaded `run` as one autograd node: sf_ngp_render_shaded_forward_train / sf_ngp_render_shaded_backward
+    (csrc/ngp_shade.h, csrc/ngp_shade_bwd.h).  Differentiable outputs: image, weights_sum and the per-ray orientation term; the
+    gradient reaches the field parameters only (albedo, and the density through the finite-difference normal).  A sample whose
+    finite-difference gradient has a non-finite component passes nothing through its normal -- a deliberate deviation: torch would
+    write NaN into every parameter."""
+
+    @staticmethod
+    def forward(ctx, handle, rays_o, rays_d, aabb, T, min_near, lin, u_coarse, u_fine, u_stride, bg, rays_per_row, light, ratio, epsilon,
+                *params):
+        _lib.require_cuda(rays_o, rays_d, aabb, light, *params)
+        params = [p.detach().contiguous() for p in params]
+        N, dev = rays_o.shape[0], rays_o.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        nears, fars = torch.empty(N, **f32), torch.empty(N, **f32)
+        z_s, sig_s, w_s = (torch.empty(N, 2 * T, **f32) for _ in range(3))
+        rgb_s, nrm_s, col_s, grad_s = (torch.empty(N, 2 * T, 3, **f32) for _ in range(4))
+        image, nimg = torch.empty(N, 3, **f32), torch.empty(N, 3, **f32)
+        depth, ws, orient = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, **f32)
+        lib = _lib.lib()
+        wbytes = lib.sf_ngp_render_shaded_workspace_bytes(N, T)
+        work = torch.empty(max(1, wbytes // 4), **f32)
+        f = handle.struct(params)
+        _select_field_kernel(lib)
+        rc = lib.sf_ngp_render_shaded_forward_train(
+            C.byref(f), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(aabb), N, T, float(min_near), _lib.ptr(lin), _lib.ptr(u_coarse),
+            _lib.ptr(u_fine), int(u_stride), float(bg), _lib.ptr(light), float(ratio), float(epsilon), _lib.ptr(nears), _lib.ptr(fars),
+            _lib.ptr(z_s), _lib.ptr(sig_s), _lib.ptr(rgb_s), _lib.ptr(nrm_s), _lib.ptr(col_s), _lib.ptr(grad_s), _lib.ptr(w_s),
+            _lib.ptr(image), _lib.ptr(nimg), _lib.ptr(orient), _lib.ptr(depth), _lib.ptr(ws), _lib.ptr(work), wbytes, _lib.stream_ptr())
+        _lib.check(rc, "ngp_render_shaded_forward_train")
+        ctx.handle, ctx.T, ctx.bg, ctx.rays_per_row = handle, T, float(bg), int(rays_per_row)
+        ctx.ratio, ctx.epsilon = float(ratio), float(epsilon)
+        ctx.save_for_backward(rays_o, rays_d, aabb, nears, fars, z_s, sig_s, rgb_s, nrm_s, col_s, grad_s, w_s, light, *params)
+        ctx.mark_non_differentiable(depth, nimg, nears, fars)
+        return image, ws, orient, depth, nimg, nears, fars
+
+    @staticmethod
+    def backward(ctx, g_image, g_ws, g_orient, _gd, _gn, _gnear, _gfar):
+        rays_o, rays_d, aabb, nears, fars, z_s, sig_s, rgb_s, nrm_s, col_s, grad_s, w_s, light, *params = ctx.saved_tensors
+        N, T, dev = rays_o.shape[0], ctx.T, rays_o.device
+        # a frozen table is a null g_embeddings (no d(feat), no scatter)
+        needs = ctx.needs_input_grad[15:]
+        grads = [torch.zeros_like(p) if (i > 0 or needs[0]) else None for i, p in enumerate(params)]
+        g = _lib.SfNgpFieldGrad()
+        (g.g_embeddings, g.g_w0, g.g_b0, g.g_w1, g.g_b1, g.g_w2, g.g_b2) = (t.data_ptr() if t is not None else None for t in grads)
+        f = ctx.handle.struct(params)
+        lib = _lib.lib()
+        wbytes = lib.sf_ngp_render_shaded_backward_workspace_bytes(N, T)
+        work = torch.empty(max(1, wbytes // 4), dtype=torch.float32, device=dev)
+        g_image = (g_image if g_image is not None else torch.zeros(N, 3, device=dev)).contiguous().float()
+        g_ws = g_ws.contiguous().float() if g_ws is not None else None
+        g_orient = g_orient.contiguous().float() if g_orient is not None else None
+        rc = lib.sf_ngp_render_shaded_backward(
+            C.byref(f), C.byref(g), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(aabb), N, T, _lib.ptr(nears), _lib.ptr(fars),
+            _lib.ptr(z_s), _lib.ptr(sig_s), _lib.ptr(rgb_s), _lib.ptr(nrm_s), _lib.ptr(col_s), _lib.ptr(grad_s), _lib.ptr(w_s),
+            _lib.ptr(light), ctx.ratio, ctx.epsilon, ctx.bg, _lib.ptr(g_image), _lib.ptr(g_ws), _lib.ptr(g_orient),
+            int(ctx.rays_per_row), _lib.ptr(work), wbytes, _lib.stream_ptr())
+        _lib.check(rc, "ngp_render_shaded_backward")
+        return (None,) * 15 + tuple(grads)
 
 
 class NeRFRenderer(nn.Module):
@@ -383,8 +445,14 @@ class NeRFRenderer(nn.Module):
 
         shading='albedo': the differentiable fused render.  shading='lambertian' (renderer_df.py:404-456): the same samples, then per
         sorted sample the finite-difference normal (epsilon 1e-2, the reference's) and albedo * (ambient_ratio + (1 - ambient_ratio)
-        * max(n . -light_d, 0)), composited -- one no-gradient entry (sf_ngp_render_shaded_forward), so it is allowed when grad mode
-        is off or no field parameter requires grad, and raises otherwise.  `light_d`: any 3-vector; None draws
+        * max(n . -light_d, 0)), composited -- by default one no-gradient entry (sf_ngp_render_shaded_forward), so it is allowed when
+        grad mode is off or no field parameter requires grad, and raises otherwise.  With the keyword `shading_backward=True` (an
+        extension; it travels in **vars(opt) as `w` / `h` do, opt.shading_backward) the shaded render is differentiable instead: the
+        same samples, draws and values through one autograd node (sf_ngp_render_shaded_forward_train / _backward): the gradient of
+        'image', 'weights_sum' and 'loss_orient' reaches the albedo and, through the normal, the six offset densities of every
+        sample; the weights inside 'loss_orient' are detached as in the reference (:430); a sample whose finite-difference gradient
+        is not finite passes nothing through its normal (torch would write NaN into every parameter); light_d, the rays and
+        'normal' get no gradient.  `light_d`: any 3-vector; None draws
         safe_normalize(rays_o[0] + randn(3)) (the draw an albedo render consumes at the same place) or, with fixed_light, the
         reference's rotation of rays_o[0] (:345-348).  The result then also holds 'loss_orient' (mean over all N * 2T samples of
         w * max(n . d, 0)^2, the reference's) and 'normal' [..., 3] = sum w n, the normal image -- an extension: the reference
@@ -397,7 +465,8 @@ class NeRFRenderer(nn.Module):
         if num_steps != upsample_steps:
             raise NotImplementedError("the fused render needs num_steps == upsample_steps (reference: 64/64)")
         shaded = shading == 'lambertian'
-        if shaded and torch.is_grad_enabled() and any(q.requires_grad for q in self._field_params()):
+        shaded_bwd = shaded and bool(kwargs.get('shading_backward', False))
+        if shaded and not shaded_bwd and torch.is_grad_enabled() and any(q.requires_grad for q in self._field_params()):
             raise NotImplementedError("the shaded render has no backward: call it under torch.no_grad() or with a frozen field "
                                       "(shading='albedo' is the differentiable render)")
         if shaded and light_d is not None:
@@ -433,6 +502,12 @@ class NeRFRenderer(nn.Module):
             bg_color = 1
         if torch.is_tensor(bg_color):
             raise NotImplementedError("per-ray bg_color tensors are not on the distillation path (bg_color=0)")
+        if shaded_bwd:
+            image, weights_sum, orient, depth, nimg, nears, fars = _ShadedRenderFn.apply(
+                self._field_handle(), o, d, aabb, T, self.min_near, lin, u_coarse, u_f, stride, float(bg_color),
+                self._rays_per_row(N, kwargs), light.contiguous(), float(ambient_ratio), 1e-2, *self._field_params())
+            return {'image': image.view(*prefix, 3), 'depth': depth.view(*prefix), 'weights_sum': weights_sum,
+                    'mask': (nears < fars).view(*prefix), 'loss_orient': orient.sum() / max(1, N * 2 * T), 'normal': nimg.view(*prefix, 3)}
         if shaded:
             return self._run_shaded(prefix, o, d, aabb, T, lin, u_coarse, u_f, stride, float(bg_color), light.contiguous(),
                                     float(ambient_ratio))

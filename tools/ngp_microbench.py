@@ -2,6 +2,11 @@
 --shading lambertian adds, after the default output: the shaded render (sf_ngp_render_shaded_forward), the albedo forward at the same
 size, and the composed route (albedo forward + sf_ngp_point_attrs over the sorted points + torch glue for the weights and the sums),
 each the median of 5 torch-event timings after a warm-up.
+--shading lambertian --backward times instead the DIFFERENTIABLE shaded render, forward + backward of image.mean() + weights_sum.mean()
++ loss_orient: the fused route (run(shading='lambertian', shading_backward=True): sf_ngp_render_shaded_forward_train / _backward), the
+albedo render's forward + backward at the same size, and the composed route -- the albedo forward for the sorted ray, then
+NeRFNetwork.forward(x, d, l, ratio, 'lambertian') under autograd on the sorted points (seven field evaluations through the grid-encode
+op) and torch compositing.
 --bwd-pipe 0|1 selects the kernel of the cached field backward (renderer._FIELD_BWD_PIPE) instead of the default.
 --feat-cache 0|1 sets renderer._FEAT_CACHE: 0 = no field cache, the backward re-gathers the features (k_ngp_field_bwd_mfma)."""
 import os
@@ -109,5 +114,71 @@ def shaded_times():
     print(f"composed shaded : {median_ms(composed):.3f} ms")
 
 
+def shaded_backward_times():
+    import ctypes as C
+    from sparsefusion_amd import _lib
+    light = torch.tensor([0.3, -0.5, 0.81], device=dev)
+    light = light / light.norm()
+    ratio, T = 0.1, net.opt.num_steps
+    of, df = o[0].contiguous(), d[0].contiguous()
+    N = of.shape[0]
+
+    def fused():
+        net.zero_grad(set_to_none=True)
+        r = net.render(o, d, **dict(kw, shading='lambertian', light_d=light, ambient_ratio=ratio, shading_backward=True))
+        (r["image"].mean() + r["weights_sum"].mean() + r["loss_orient"]).backward()
+
+    def albedo():
+        net.zero_grad(set_to_none=True)
+        r = net.render(o, d, **kw)
+        (r["image"].mean() + r["weights_sum"].mean()).backward()
+
+    def composed():
+        net.zero_grad(set_to_none=True)
+        f32 = dict(dtype=torch.float32, device=dev)
+        lin, det = net._table(T, of.device)
+        params = [q.detach().contiguous() for q in net._field_params()]
+        f = net._field_handle().struct(params)
+        lib = _lib.lib()
+        nears, fars, depth, ws = (torch.empty(N, **f32) for _ in range(4))
+        z_s, sig_s, rgb_s, image = torch.empty(N, 2 * T, **f32), torch.empty(N, 2 * T, **f32), torch.empty(N, 2 * T, 3, **f32), torch.empty(N, 3, **f32)
+        wbytes = lib.sf_ngp_render_forward_workspace_bytes(N, T)
+        work = torch.empty(wbytes // 4, **f32)
+        u_c, u_fine = torch.rand(N, T, device=dev), torch.rand(N, T, device=dev)
+        _lib.check(lib.sf_ngp_render_forward(C.byref(f), _lib.ptr(of), _lib.ptr(df), _lib.ptr(net.aabb_train), N, T, float(net.min_near),
+                                             _lib.ptr(lin), _lib.ptr(u_c), _lib.ptr(u_fine), T, 0.0, _lib.ptr(nears), _lib.ptr(fars), _lib.ptr(z_s),
+                                             _lib.ptr(sig_s), _lib.ptr(rgb_s), _lib.ptr(image), _lib.ptr(depth), _lib.ptr(ws), None,
+                                             _lib.ptr(work), wbytes, _lib.stream_ptr()), "ngp_render_forward")
+        x = torch.min(torch.max(of[:, None] + df[:, None] * z_s[..., None], net.aabb_train[:3]), net.aabb_train[3:])
+        dirs = df[:, None].expand(N, 2 * T, 3)
+        sigma, col, n = net(x.view(-1, 3), dirs.reshape(-1, 3), light, ratio=ratio, shading='lambertian')
+        sigma, col, n = sigma.view(N, 2 * T), col.view(N, 2 * T, 3), n.view(N, 2 * T, 3)
+        deltas = torch.cat([z_s[:, 1:] - z_s[:, :-1], ((fars - nears) / T)[:, None]], -1)
+        alphas = 1 - torch.exp(-deltas * sigma)
+        w = alphas * torch.cumprod(torch.cat([torch.ones_like(alphas[:, :1]), 1 - alphas + 1e-15], -1), -1)[:, :-1]
+        img = (w[..., None] * col).sum(-2)
+        orient = (w.detach() * (n * dirs).sum(-1).clamp(min=0) ** 2).mean()
+        (img.mean() + w.sum(-1).mean() + orient).backward()
+
+    def median_ms(fn):
+        fn()
+        ts = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return sorted(ts)[2]
+
+    print(f"shaded fwd+bwd  : {median_ms(fused):.3f} ms   (fused: sf_ngp_render_shaded_forward_train + sf_ngp_render_shaded_backward)")
+    print(f"albedo fwd+bwd  : {median_ms(albedo):.3f} ms")
+    print(f"composed fwd+bwd: {median_ms(composed):.3f} ms   (albedo forward + NeRFNetwork.forward('lambertian') under autograd + torch compositing)")
+
+
 if "--shading" in sys.argv and sys.argv[sys.argv.index("--shading") + 1:][:1] == ["lambertian"]:
-    shaded_times()
+    if "--backward" in sys.argv:
+        shaded_backward_times()
+    else:
+        shaded_times()
