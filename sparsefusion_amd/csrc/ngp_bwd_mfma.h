@@ -17,7 +17,7 @@
 #pragma once
 #include "sf_dev.h"
 #include "ngp_device.h"
-#include "ngp_point_attrs.h"                       // ngp_offset_point
+#include "ngp_point_attrs.h"                       // ngp_sample_x01
 
 #define FB_PTS 32
 #define FB_SF 33                                   // feat row stride (floats)
@@ -100,17 +100,7 @@ SF_KERNEL(256) void k_ngp_field_bwd_mfma_t(FBArgs a) {
     const bool live = p < a.P;
     float x[3] = {0.f, 0.f, 0.f}, x01[3] = {0.f, 0.f, 0.f};
     bool inside = false;
-    if (live) {
-      const uint32_t n = p / a.T2;
-      const float o[3] = {a.rays_o[n * 3], a.rays_o[n * 3 + 1], a.rays_o[n * 3 + 2]};
-      const float d[3] = {a.rays_d[n * 3], a.rays_d[n * 3 + 1], a.rays_d[n * 3 + 2]};
-      ngp_point(o, d, a.z_s[p], box, x);
-      if (OFF) {
-        const float xc[3] = {x[0], x[1], x[2]};
-        ngp_offset_point(xc, (int)a.off_e, a.off_eps, a.bound, x);
-      }
-      inside = ngp_unit(x, a.bound, x01);
-    }
+    if (live) inside = ngp_sample_x01<OFF>(a.rays_o, a.rays_d, p / a.T2, a.z_s[p], box, a.bound, a.off_e, a.off_eps, x, x01);
     if (!OFF && a.feat_c) {
       // cached features: this lane's 16 floats (levels half*8 .. half*8+7) of the sample's row
       f32x4 fv[4];

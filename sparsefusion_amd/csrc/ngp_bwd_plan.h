@@ -82,8 +82,8 @@ static inline uint64_t ngp_render_workspace_bytes(uint32_t N, uint32_t T) {
 }
 static inline uint64_t ngp_render_forward_workspace_bytes(uint32_t N, uint32_t T) { return (uint64_t)10 * N * T * sizeof(float); }
 
-// Which kernel scatters which level of the table gradient: levels [0, last) go to k_ngp_scatter, [0, cached) of them through its LDS cache;
-// levels [last, L) go to the binned scatter (binned) or to k_ngp_scatter_fine, chunk by chunk.  bucket0[l]: first bucket of level l,
+// Which kernel scatters which level of the table gradient: levels [0, last) go to k_ngp_scatter (ngp_scatter.h), [0, cached) of them through
+// its LDS cache; levels [last, L) go to the binned scatter (binned; ngp_scatter_bin.h) or to k_ngp_scatter_fine (ngp_scatter.h), chunk by chunk.  bucket0[l]: first bucket of level l,
 // total_buckets of bin_cap entries each.
 struct NgpScatterPlan {
   uint32_t cached, first_bin, last, total_buckets, bin_cap;

@@ -391,9 +391,15 @@ SF_HD void ngp_mlp_backward(const float* __restrict__ W, const float h1[NGP_HID]
   }
 }
 
+// A `tiled` level whose (res+1)^2 already exceeds the level size while res+1 does not: the index rule of ngp_row3 drops z
+// (gridencoder.cu:60), so corners i and i + 4 of every cell share their row.  The one statement of the rule for every scatter kernel.
+SF_HD bool ngp_z_dropped(const NgpLevels& lv, uint32_t l) {
+  const uint32_t step = lv.resolution[l] + 1;
+  return lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
+}
+
 // Scatter d(loss)/d(features) of ONE point into the table gradient (kernel_grid_backward,
-// gridencoder.cu:226-313) -- hardware fp32 atomics on the GPU.  On tiled levels whose (res+1)^2 already
-// exceeds the level size the index rule drops z (gridencoder.cu:60), so the two z-corners of every (x,y)
+// gridencoder.cu:226-313) -- hardware fp32 atomics on the GPU.  On z-dropped levels the two z-corners of every (x,y)
 // pair hit the SAME row with weights w_xy*(1-pz) and w_xy*pz: they are merged into one add of w_xy*g
 // (identical sum, half the atomics on levels >= 7 of the reference geometry).
 SF_HD void ngp_scatter(const NgpLevels& lv, float* __restrict__ gtable, const float x01[3], bool inside,
@@ -405,9 +411,7 @@ SF_HD void ngp_scatter(const NgpLevels& lv, float* __restrict__ gtable, const fl
       NgpCell c;
       ngp_cell(lv, l, x01, c);
       float* tab = gtable + (size_t)lv.offset[l] * 2;
-      const uint32_t step = lv.resolution[l] + 1;
-      const bool z_dropped = lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
-      if (z_dropped) {
+      if (ngp_z_dropped(lv, l)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                  // corners i and i+4 differ only in z
           const float w = SF_ADD(c.w[i], c.w[i + 4]);

@@ -22,13 +22,31 @@ struct NgpPointAttrs { float sigma; float albedo[3]; float grad[3]; float normal
 SF_HD float ngp_clamp_sym(float v, float b) { return (v != v) ? v : fminf(fmaxf(v, -b), b); }
 
 // Offset point e = 1 .. 6 of x (the rule in the header comment).  One function for the forward (ngp_point_attrs below) and for the
-// offset instantiations of the backward kernels (ngp_bwd_mfma.h, ngp_scatter_bin.h, ngp_render.hip): the backward's point is the
-// forward's fp32 point bit for bit.
+// offset instantiations of the backward kernels (through ngp_sample_x01 below, or called by the kernel itself): the backward's point is
+// the forward's fp32 point bit for bit.
 SF_HD void ngp_offset_point(const float x[3], int e, float eps, float bound, float xe[3]) {
   const int axis = (e - 1) >> 1;
   const float o = (e & 1) ? eps : -eps;
 #pragma unroll
   for (int d = 0; d < 3; ++d) xe[d] = ngp_clamp_sym(SF_ADD(x[d], d == axis ? o : 0.0f), bound);
+}
+
+// The point a backward kernel gathers from or scatters to, for the sorted sample at depth z of ray n: ngp_point, with OFF = 1 then offset
+// point off_e = 1 .. 6 of it with step off_eps (OFF = 0 ignores both), then ngp_unit.  x: the world point, x01: its unit-cube image;
+// returns whether it lies inside the grid.  Used by k_ngp_field_bwd_mfma_t (ngp_bwd_mfma.h), k_ngp_scatter_fine (ngp_scatter.h) and the
+// references of tests/hostemu.  k_ngp_scatter (ngp_scatter.h) and k_ngp_bin_t (ngp_scatter_bin.h), the two scatter kernels of every
+// teacher-field backward, restate these steps in their own text: that is the code their timing was measured on (the reasons are there).
+template <int OFF>
+SF_HD bool ngp_sample_x01(const float* __restrict__ rays_o, const float* __restrict__ rays_d, uint32_t n, float z, const float box[6],
+                          float bound, uint32_t off_e, float off_eps, float x[3], float x01[3]) {
+  const float o[3] = {rays_o[n * 3], rays_o[n * 3 + 1], rays_o[n * 3 + 2]};
+  const float d[3] = {rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2]};
+  ngp_point(o, d, z, box, x);
+  if (OFF) {
+    const float xc[3] = {x[0], x[1], x[2]};
+    ngp_offset_point(xc, (int)off_e, off_eps, bound, x);
+  }
+  return ngp_unit(x, bound, x01);
 }
 
 // The finite-difference arithmetic, shared by ngp_point_attrs below and the eight-lanes-per-ray shaded render (ngp_occ_shade.h),

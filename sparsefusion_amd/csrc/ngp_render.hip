@@ -12,9 +12,11 @@
 //     per-thread scratch columns live in LDS ([k][lane] layout: bank-conflict free);
 //   * backward RECOMPUTES the field forward instead of saving activations (VALU is cheap, HBM is
 //     not); MLP weight gradients are formed per 256-point tile as LDS-staged outer-product
-//     sums, one atomic flush per workgroup; table gradients use fp32 L2 atomics.
-// Per-thread math lives in ngp_device.h, the backward's host plan (chunks, launch geometry, level split, workspace sizes) in
-// ngp_bwd_plan.h (both also compiled for the host by tests/hostemu).
+//     sums, one atomic flush per workgroup; table gradients are scattered with device atomics (ngp_scatter.h) or binned and reduced
+//     in LDS (ngp_scatter_bin.h).
+// This file keeps the host code, k_ngp_field, k_ngp_sample_fine and k_fix_to_f32; every other kernel lives in a header written against
+// sf_dev.h.  Per-thread math lives in ngp_device.h, the backward's host plan (chunks, launch geometry, level split, workspace sizes) in
+// ngp_bwd_plan.h (all also compiled for the host by tests/hostemu).
 //
 // Layouts (row-major): z_c,sig_c [N,T]; rgb_c [N,T,3]; z_f,sig_f,rgb_f same; z_sorted,sigma_s
 // [N,2T]; rgb_s [N,2T,3]; image [N,3]; depth, weights_sum, nears, fars [N].
@@ -27,6 +29,7 @@
 #include "ngp_bwd_pipe.h"
 #include "ngp_field_mfma.h"
 #include "ngp_composite_wave.h"
+#include "ngp_scatter.h"
 #include "ngp_scatter_bin.h"
 #include "ngp_shade.h"
 #include "ngp_shade_bwd.h"
@@ -103,191 +106,6 @@ __global__ __launch_bounds__(64) void k_ngp_sample_fine(
   SfCol bins{smem + (size_t)T * 64 + threadIdx.x, 64};
   ngp_sample_fine(z_c + (size_t)n * T, sig_c + (size_t)n * T, u + (size_t)n * u_row_stride, nears[n], fars[n], T,
                   cdf, bins, z_f + (size_t)n * T);
-}
-
-// ---------------------------------------------------------------------------
-// Table-gradient scatter.  Device-memory fp32 atomics execute at the memory side on MI355X (the 8 XCD
-// L2s are not coherent): ~17 G scattered lane-ops/s, so the scatter is bound by the NUMBER of atomics.
-// One workgroup owns a tile of 64 rays (an 8x8 image patch when the ray layout is known) = 8192 sorted
-// samples, and walks the levels one at a time:
-//   * coarse levels (cell larger than the patch footprint): contributions are first summed in an LDS
-//     direct-mapped cache keyed by table row (LDS atomics are ~free), then each touched row is flushed
-//     with ONE pair of global atomics per workgroup -- >95 % fewer global atomics on levels 0-5;
-//   * fine levels: direct global atomics, z-corner pairs merged on z-dropped levels (ngp_scatter rule).
-// ---------------------------------------------------------------------------
-#define SC_RAYS 64
-#define SC_SLOTS 4096
-#define SC_EMPTY 0xffffffffu
-#ifndef SC_RUN
-#define SC_RUN 32u              // sorted samples merged per thread before the cache (`sc_run` below; measured with the level split, ngp_bwd_plan.h)
-#endif
-// NT threads share one 80 KB LDS cache (4096 slots of 64-bit fixed-point sums; r02: 8192 of floats) (one workgroup per CU): NT = 1024 puts 4 waves on every SIMD -- the loop body is a
-// chain of dependent global loads, hash arithmetic and LDS atomics, and with the first version's 256 threads (ONE wave per
-// SIMD) every one of those latencies was exposed.  `last_level`: levels [0, last_level) are walked by this kernel.
-// OFF = 1 (here and in k_ngp_scatter_fine): the points are offset point `off_e` (1 .. 6, ngp_point_attrs.h) of every sample, step
-// `off_eps` -- the finite-difference passes of the shaded backward.  OFF = 0 ignores both.
-template <int NT, int OFF = 0>
-__global__ __launch_bounds__(NT) void k_ngp_scatter(
-    NgpLevels lv, float bound, long long* __restrict__ gtable, float* __restrict__ gtable_f, float thr, const float* __restrict__ rays_o,
-    const float* __restrict__ rays_d, const float* __restrict__ aabb, const float* __restrict__ z_s,
-    const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t rays_per_row, uint32_t cached_levels,
-    uint32_t last_level, uint32_t sc_run, uint32_t off_e, float off_eps) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  uint32_t* tags = reinterpret_cast<uint32_t*>(smem);            // [SC_SLOTS]
-  long long* vals = reinterpret_cast<long long*>(smem + SC_SLOTS);   // [SC_SLOTS][2], fixed point (sf_dev.h): exact, order-independent sums
-  const uint32_t P = N * T2;
-  float box[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) box[i] = aabb[i];
-  // tile -> ray ids: 8x8 patch of the image if the layout is known, else 64 consecutive rays
-  uint32_t tile_x = 0, tile_y = 0, tiles_x = 0;
-  const bool patch = rays_per_row >= 8 && (rays_per_row % 8) == 0 && (N % rays_per_row) == 0 && ((N / rays_per_row) % 8) == 0;
-  if (patch) { tiles_x = rays_per_row / 8; tile_y = blockIdx.x / tiles_x; tile_x = blockIdx.x % tiles_x; }
-
-  for (uint32_t l = 0; l < last_level; ++l) {
-    const bool cached = l < cached_levels;
-    if (cached) {
-      for (uint32_t s = threadIdx.x; s < SC_SLOTS; s += NT) { tags[s] = SC_EMPTY; vals[2 * s] = 0; vals[2 * s + 1] = 0; }
-      __syncthreads();
-    }
-    long long* tab = gtable + (size_t)lv.offset[l] * 2;
-    float* ftab = gtable_f + (size_t)lv.offset[l] * 2;
-    const uint32_t step = lv.resolution[l] + 1;
-    const bool z_dropped = lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
-    // lane quads share a sample: lane&1 = channel, lane&2 = x-corner.  The four adds of an x-corner pair (two
-    // adjacent table rows x 2 channels = 16 contiguous bytes) sit in adjacent lanes of ONE atomic instruction: the
-    // memory-side atomic unit merges lanes of one granule (measured 13.5 -> 7.6 ms with channel pairs alone).
-    // A thread-item = (ray, run of `sc_run` consecutive sorted samples, lane of the quad).  Consecutive samples of a ray share
-    // their cell on the coarse levels, so equal rows are first summed in REGISTERS (run-length merge per corner pair) and
-    // only the run totals go to the LDS cache: on levels 0-5 nearly every lane of every atomic instruction used to hit
-    // the same handful of LDS addresses, and same-address LDS atomics serialise (0.18 ms per level for ~1 us of work).
-    const uint32_t runs = (T2 + sc_run - 1) / sc_run;
-    auto flush = [&](uint32_t row, float v, uint32_t ch) {
-      if (!(fabsf(v) < thr)) {                                   // large / non-finite: the fp32 table (sf_grad_add)
-        sf_global_add(ftab + (size_t)row * 2 + ch, v);
-        return;
-      }
-      if (cached) {
-        const uint32_t slot = (row * 2654435761u) >> 20;         // 12 bits -> SC_SLOTS
-        const uint32_t prev = atomicCAS(&tags[slot], SC_EMPTY, row);
-        if (prev == SC_EMPTY || prev == row) {
-          sf_fix_add(&vals[2 * slot + ch], sf_fix_of(v));
-          return;
-        }
-      }
-      sf_fix_add(tab + (size_t)row * 2 + ch, sf_fix_of(v));
-    };
-    for (uint32_t it = threadIdx.x; it < 4 * SC_RAYS * runs; it += NT) {
-      const uint32_t q = it >> 2, ch = it & 1, xb = (it >> 1) & 1;
-      const uint32_t r = q / runs, k0 = (q - r * runs) * sc_run;
-      uint32_t n = patch ? ((tile_y * 8 + (r >> 3)) * rays_per_row + tile_x * 8 + (r & 7)) : (blockIdx.x * SC_RAYS + r);
-      if (n >= N) continue;
-      const float o[3] = {rays_o[n * 3], rays_o[n * 3 + 1], rays_o[n * 3 + 2]};
-      const float d[3] = {rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2]};
-      uint32_t prow[4] = {SC_EMPTY, SC_EMPTY, SC_EMPTY, SC_EMPTY};
-      float pacc[4] = {0.f, 0.f, 0.f, 0.f};
-      const uint32_t k1 = k0 + sc_run < T2 ? k0 + sc_run : T2;
-      // (r04: the run walked in batches of 4 / 8 / 16 samples with their gradient and depth loads issued together measured SLOWER,
-      // 3.76 / 3.76 / 3.86 against 3.55 ms render fwd + bwd, profiles/r04_ngp_binned_tuning.log: 128 VGPRs at 1024 threads, and the
-      // kernel runs beside the last chunk's bin + reduce, whose memory traffic it then competes with)
-      for (uint32_t k = k0; k < k1; ++k) {
-        const uint32_t p = n * T2 + k;
-        const float dfc = dfeat[((size_t)l * P + p) * 2 + ch];
-        if (dfc == 0.0f) continue;                               // outside points / dead samples contribute nothing
-        float x[3], x01[3];
-        ngp_point(o, d, z_s[p], box, x);
-        if (OFF) {
-          const float xc[3] = {x[0], x[1], x[2]};
-          ngp_offset_point(xc, (int)off_e, off_eps, bound, x);
-        }
-        if (!ngp_unit(x, bound, x01)) continue;
-        NgpCell c;
-        ngp_cell(lv, l, x01, c);
-#pragma unroll
-        for (int yz = 0; yz < 4; ++yz) {
-          if (z_dropped && yz >= 2) continue;
-          const int i0 = yz << 1, i1 = i0 | 1;        // the two x-corners of this (y, z) corner pair
-          const float w0 = z_dropped ? SF_ADD(c.w[i0 & 3], c.w[(i0 & 3) + 4]) : c.w[i0];
-          const float w1 = z_dropped ? SF_ADD(c.w[i1 & 3], c.w[(i1 & 3) + 4]) : c.w[i1];
-          const float w = xb ? w1 : w0;
-          const uint32_t row = xb ? c.row[i1] : c.row[i0];
-          const float v = SF_MUL(w, dfc);
-          if (row == prow[yz]) {
-            pacc[yz] += v;
-          } else {
-            if (prow[yz] != SC_EMPTY) flush(prow[yz], pacc[yz], ch);
-            prow[yz] = row;
-            pacc[yz] = v;
-          }
-        }
-      }
-#pragma unroll
-      for (int yz = 0; yz < 4; ++yz)
-        if (prow[yz] != SC_EMPTY) flush(prow[yz], pacc[yz], ch);
-    }
-    if (cached) {
-      __syncthreads();
-      for (uint32_t s = threadIdx.x; s < SC_SLOTS; s += NT) {
-        const uint32_t row = tags[s];
-        if (row != SC_EMPTY) {
-          if (vals[2 * s]) sf_fix_add(tab + (size_t)row * 2, vals[2 * s]);
-          if (vals[2 * s + 1]) sf_fix_add(tab + (size_t)row * 2 + 1, vals[2 * s + 1]);
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// Fine levels (cell smaller than the patch footprint: nothing to merge in LDS): no LDS frame, so 8 waves per SIMD hide the
-// latency of the loads in front of every atomic.  Work item = (level, sample) in level-major order (the dfeat layout),
-// lane quads as above: 16 contiguous bytes per atomic instruction and quad.
-template <int OFF>
-__global__ __launch_bounds__(256) void k_ngp_scatter_fine(
-    NgpLevels lv, float bound, long long* __restrict__ gtable, float* __restrict__ gtable_f, float thr, const float* __restrict__ rays_o,
-    const float* __restrict__ rays_d, const float* __restrict__ aabb, const float* __restrict__ z_s,
-    const float* __restrict__ dfeat, uint32_t N, uint32_t T2, uint32_t first_level, uint32_t P_stride, uint32_t p_off, uint32_t off_e,
-    float off_eps) {
-  // this launch walks the N rays behind the (pre-offset) ray / sample pointers = points [p_off, p_off + N * T2) of a set of
-  // P_stride points, whose level-major layout dfeat keeps
-  const uint32_t P = N * T2;
-  float box[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) box[i] = aabb[i];
-  const uint64_t total = (uint64_t)4 * P * (lv.L - first_level);
-  for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (uint64_t)gridDim.x * 256) {
-    const uint32_t ch = (uint32_t)it & 1, xb = ((uint32_t)it >> 1) & 1;
-    const uint64_t q = it >> 2;
-    const uint32_t l = first_level + (uint32_t)(q / P), p = (uint32_t)(q % P);
-    const float dfc = dfeat[((size_t)l * P_stride + p_off + p) * 2 + ch];
-    if (dfc == 0.0f) continue;
-    const uint32_t n = p / T2;
-    const float o[3] = {rays_o[n * 3], rays_o[n * 3 + 1], rays_o[n * 3 + 2]};
-    const float d[3] = {rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2]};
-    float x[3], x01[3];
-    ngp_point(o, d, z_s[p], box, x);
-    if (OFF) {
-      const float xc[3] = {x[0], x[1], x[2]};
-      ngp_offset_point(xc, (int)off_e, off_eps, bound, x);
-    }
-    if (!ngp_unit(x, bound, x01)) continue;
-    NgpCell c;
-    ngp_cell(lv, l, x01, c);
-    long long* tab = gtable + (size_t)lv.offset[l] * 2;
-    float* ftab = gtable_f + (size_t)lv.offset[l] * 2;
-    const uint32_t step = lv.resolution[l] + 1;
-    const bool z_dropped = lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) {
-      if (z_dropped && yz >= 2) continue;
-      const int i0 = yz << 1, i1 = i0 | 1;
-      const float w0 = z_dropped ? SF_ADD(c.w[i0 & 3], c.w[(i0 & 3) + 4]) : c.w[i0];
-      const float w1 = z_dropped ? SF_ADD(c.w[i1 & 3], c.w[(i1 & 3) + 4]) : c.w[i1];
-      const float w = xb ? w1 : w0;
-      const uint32_t row = xb ? c.row[i1] : c.row[i0];
-      sf_grad_add(tab + (size_t)row * 2 + ch, ftab + (size_t)row * 2 + ch, SF_MUL(w, dfc), thr);
-    }
-  }
 }
 
 // Fixed-point gradient sums (sf_dev.h) -> the caller's fp32 gradients: dst[i] += acc[i] * 2^-44.  Segments are consecutive in acc.
@@ -519,12 +337,11 @@ extern "C" int sf_ngp_render_shaded_forward_train(const sf_ngp_field* f, const f
 // backward: what the library keeps per device, and the two guards of a call
 // ---------------------------------------------------------------------------
 static constexpr size_t FB_LDS_BYTES = (size_t)FB_LDS_FLOATS * sizeof(float);
-static constexpr size_t SC_LDS_BYTES = (size_t)SC_SLOTS * (sizeof(uint32_t) + 2 * sizeof(long long));
 
 static int ngp_bwd_raise_lds_limits() {             // raised dynamic-LDS limits are per-device function attributes
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma_t<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_field_bwd_mfma_t<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB_LDS_BYTES) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ngp_scatter<1024, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_LDS_BYTES) != hipSuccess)
     SF_FAIL(SF_ERR_LAUNCH, "ngp_render_backward: cannot raise the dynamic LDS limits");
@@ -702,6 +519,9 @@ static int ngp_bwd_field_scatter(const sf_ngp_field* f, const sf_ngp_field_grad*
   SBRArgs r{};
   r.lv = lv; r.gtable = acc_tab; r.gtable_f = g->g_embeddings; r.thr = thr_tab; r.cursor = bin_cursor; r.ent = bin_ent; r.first_level = sp.first_bin; r.cap = sp.bin_cap;
   for (uint32_t l = 0; l <= NGP_MAX_LEVELS; ++l) { b.bucket0[l] = sp.bucket0[l]; r.bucket0[l] = sp.bucket0[l]; }
+  SCArgs s{};                                       // k_ngp_scatter_fine (ngp_scatter.h): the rays of a launch are set at the launch
+  s.lv = lv; s.bound = f->bound; s.aabb = aabb; s.dfeat = dfeat; s.gtable = acc_tab; s.gtable_f = g->g_embeddings; s.thr = thr_tab; s.T2 = T2;
+  s.first_level = sp.last; s.P_stride = (uint32_t)M;
 
   // ---- the pipeline (r03).  Three kernels with three different bottlenecks: the field backward (fp32 MFMA + 113 KB of LDS,
   // one workgroup per CU), the fine-level scatter (memory-side atomic unit, no LDS, VALU idle) and the cached-level scatter
@@ -718,7 +538,7 @@ static int ngp_bwd_field_scatter(const sf_ngp_field* f, const sf_ngp_field_grad*
   }
   // pass 0: the samples themselves; passes e = 1 .. 6 (the shaded backward): their offset points e
   for (uint32_t e = e_begin; e < e_end; ++e) {
-    a.off_e = e; a.off_eps = eps; b.off_e = e; b.off_eps = eps;
+    a.off_e = e; a.off_eps = eps; b.off_e = e; b.off_eps = eps; s.off_e = e; s.off_eps = eps;
     for (uint32_t c = 0; c < plan.n; ++c) {
       const uint32_t n0 = plan.start[c], Nc = plan.start[c + 1] - n0;
       const uint32_t Pc = Nc * T2, P0 = n0 * T2;
@@ -729,9 +549,7 @@ static int ngp_bwd_field_scatter(const sf_ngp_field* f, const sf_ngp_field_grad*
       const uint32_t grid = ngp_field_bwd_grid(Pc, FB_PTS);
       // with a field cache: k_ngp_field_bwd_pipe (ngp_bwd_pipe.h; same trips, same LDS image, same values) unless switched off
       const int pipe = field_cache && g_field_bwd_pipe.load(std::memory_order_relaxed) != 0 ? 1 : 0;
-      if (e) k_ngp_field_bwd_mfma_t<1><<<grid, 256, FB_LDS_BYTES, st>>>(a);
-      else if (pipe) k_ngp_field_bwd_pipe<<<grid, 256, FB_LDS_BYTES, st>>>(a);
-      else k_ngp_field_bwd_mfma_t<0><<<grid, 256, FB_LDS_BYTES, st>>>(a);
+      (e ? &k_ngp_field_bwd_mfma_t<1> : pipe ? &k_ngp_field_bwd_pipe : &k_ngp_field_bwd_mfma_t<0>)<<<grid, 256, FB_LDS_BYTES, st>>>(a);
       SF_CHECK_LAUNCH(e ? "ngp_field_bwd_mfma_off" : pipe ? "ngp_field_bwd_pipe" : "ngp_field_bwd_mfma");
       if (!e) g_field_bwd_launches[pipe].fetch_add(1, std::memory_order_relaxed);
       if (!per_chunk) continue;
@@ -740,25 +558,21 @@ static int ngp_bwd_field_scatter(const sf_ngp_field* f, const sf_ngp_field_grad*
       if (sp.binned) {
         b.rays_o = a.rays_o; b.rays_d = a.rays_d; b.z_s = a.z_s; b.P = Pc; b.p_off = P0;
         const uint32_t tiles = sf_div_up(Pc, SB_THREADS);
-        if (e) k_ngp_bin_t<1><<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
-        else k_ngp_bin_t<0><<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
+        (e ? &k_ngp_bin_t<1> : &k_ngp_bin_t<0>)<<<tiles < 1024 ? tiles : 1024, SB_THREADS, 0, sf>>>(b);
         SF_CHECK_LAUNCH("ngp_bin");
         k_ngp_bin_reduce<<<sp.total_buckets, SBR_THREADS, 0, sf>>>(r);         // leaves the cursors at zero for the next chunk
         SF_CHECK_LAUNCH("ngp_bin_reduce");
       } else {
         const uint64_t items = (uint64_t)4 * Pc * (lv.L - sp.last);
         const uint32_t grid_f = (uint32_t)(items / 256 < 16384 ? (items + 255) / 256 : 16384);
-        if (e) k_ngp_scatter_fine<1><<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2,
-                                                              sp.last, (uint32_t)M, P0, e, eps);
-        else k_ngp_scatter_fine<0><<<grid_f, 256, 0, sf>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, a.rays_o, a.rays_d, aabb, a.z_s, dfeat, Nc, T2, sp.last,
-                                                      (uint32_t)M, P0, 0u, 0.0f);
+        s.rays_o = a.rays_o; s.rays_d = a.rays_d; s.z_s = a.z_s; s.N = Nc; s.p_off = P0;
+        (e ? &k_ngp_scatter_fine<1> : &k_ngp_scatter_fine<0>)<<<grid_f, 256, 0, sf>>>(s);
         SF_CHECK_LAUNCH("ngp_scatter_fine");
       }
     }
     if (dfeat && sp.last > 0) {
       const uint32_t grid_sc = sf_div_up(N, SC_RAYS);
-      if (e) k_ngp_scatter<1024, 1><<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN, e, eps);
-      else k_ngp_scatter<1024><<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN, 0u, 0.0f);
+      (e ? &k_ngp_scatter<1024, 1> : &k_ngp_scatter<1024, 0>)<<<grid_sc, 1024, SC_LDS_BYTES, st>>>(lv, f->bound, acc_tab, g->g_embeddings, thr_tab, rays_o, rays_d, aabb, z_sorted, dfeat, N, T2, rays_per_row, sp.cached, sp.last, SC_RUN, e, eps);
       SF_CHECK_LAUNCH("ngp_scatter");
     }
     // the next pass rewrites d(feat): the side stream's last bin / scatter of this pass must have read it

@@ -3,8 +3,8 @@
 // Why.  Device-memory fp32 atomics execute at the memory side on MI355X (~20 G 16-byte granules per second, measured r02), and
 // a 128 x 128 x 128 render puts 16.8 M corner contributions into every level (the reference field, network_grid.py:63: 16 levels,
 // 2^16 rows each from level 3 on, `tiled`): on the levels whose cell is smaller than the footprint of an 8 x 8 ray patch the LDS
-// cache of k_ngp_scatter finds nothing to merge, and the backward was bound by the number of atomic granules (k_ngp_scatter_fine
-// 1.67 ms + the upper levels of k_ngp_scatter ~1.3 ms, alone).  Globally, though, every table row is hit ~256 times per render.  So:
+// cache of k_ngp_scatter (ngp_scatter.h) finds nothing to merge, and the backward was bound by the number of atomic granules
+// (k_ngp_scatter_fine 1.67 ms + the upper levels of k_ngp_scatter ~1.3 ms, alone).  Globally, though, every table row is hit ~256 times per render.  So:
 //   k_ngp_bin         one workgroup = a tile of 1024 samples, four levels at a time: the contributions of an x-corner PAIR (two table
 //                     rows, 2 x 2 values; both rows lie in one BUCKET of 1024 consecutive rows but for ~1 pair in 1024) are ranked
 //                     inside the bucket by a returning LDS atomic, the workgroup reserves a contiguous run per touched bucket with
@@ -70,10 +70,6 @@ SF_DEV f32x4 sb_pack(uint32_t r0, uint32_t r1, float w0, float w1, float d0, flo
 // Levels are taken SB_G at a time: the device atomics of a group go out together (one per thread), and a group's feature-gradient
 // rows are one batch of loads.  The ranks of a group wait in registers (16 bits each); the cells are computed again for the stores.
 #define SB_G 4
-SF_DEV bool sb_z_dropped(const NgpLevels& lv, uint32_t l) {
-  const uint32_t step = lv.resolution[l] + 1;
-  return lv.gridtype == 1 && (uint64_t)step * step > lv.hsize[l] && step <= lv.hsize[l];
-}
 // OFF = 0 is k_ngp_bin.  OFF = 1: the points are offset point a.off_e of every sample, step a.off_eps (the shaded backward; the kernel
 // itself is the template, as k_ngp_field_bwd_mfma_t)
 template <int OFF>
@@ -91,7 +87,7 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin_t(SBArgs a) {
     const uint32_t p = t0 + tid;
     bool inside = false;
     float x01[3] = {0.f, 0.f, 0.f};
-    if (p < a.P) {
+    if (p < a.P) {                                   // (the steps of ngp_sample_x01, ngp_point_attrs.h, in the order this kernel was timed with)
       const uint32_t n = p / a.T2;
       const float o[3] = {a.rays_o[n * 3], a.rays_o[n * 3 + 1], a.rays_o[n * 3 + 2]};
       const float d[3] = {a.rays_d[n * 3], a.rays_d[n * 3 + 1], a.rays_d[n * 3 + 2]};
@@ -115,7 +111,7 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin_t(SBArgs a) {
       for (int g = 0; g < SB_G; ++g) {
         const uint32_t l = l0 + g;
         if (d[g][0] != 0.0f || d[g][1] != 0.0f) {                        // outside points / dead samples contribute nothing
-          const int np = sb_z_dropped(a.lv, l) ? 2 : 4;                  // corners i and i + 4 share their row on z-dropped levels
+          const int np = ngp_z_dropped(a.lv, l) ? 2 : 4;                 // corners i and i + 4 share their row on z-dropped levels
           NgpCell c;
           ngp_cell(a.lv, l, x01, c);
           uint32_t r[4] = {0, 0, 0, 0};
@@ -139,7 +135,7 @@ SF_KERNEL(SB_THREADS) void k_ngp_bin_t(SBArgs a) {
       for (int g = 0; g < SB_G; ++g) {
         const uint32_t l = l0 + g;
         if (d[g][0] != 0.0f || d[g][1] != 0.0f) {
-          const bool zd = sb_z_dropped(a.lv, l);
+          const bool zd = ngp_z_dropped(a.lv, l);
           const int np = zd ? 2 : 4;
           NgpCell c;
           ngp_cell(a.lv, l, x01, c);

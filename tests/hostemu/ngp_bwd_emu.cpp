@@ -40,8 +40,7 @@ extern "C" void emu_field_bwd(const float* table, const int32_t* h_offsets, uint
   for (uint32_t p = 0; p < P; ++p) {
     const uint32_t n = p / T2;
     float x[3], x01[3], feat[NGP_FEAT], h1[NGP_HID], h2[NGP_HID], out[NGP_OUT], dout[NGP_OUT];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    const bool inside = ngp_unit(x, bound, x01);
+    const bool inside = ngp_sample_x01<0>(rays_o, rays_d, n, z_s[p], aabb, bound, 0, 0.0f, x, x01);
     ngp_encode(lv, table, x01, inside, feat);
     ngp_mlp_forward(W.data(), feat, h1, h2, out);
     const float pre = out[0] + ngp_blob(x);
@@ -124,8 +123,7 @@ extern "C" int emu_bin_scatter(const int32_t* h_offsets, uint32_t L, float S, ui
     for (uint32_t p = 0; p < P; ++p) {
       const uint32_t n = p / T2;
       float x[3], x01[3], df[NGP_FEAT] = {0};
-      ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-      const bool inside = ngp_unit(x, bound, x01);
+      const bool inside = ngp_sample_x01<0>(rays_o, rays_d, n, z_s[p], aabb, bound, 0, 0.0f, x, x01);
       for (uint32_t l = first_level; l < L; ++l) { df[2 * l] = dfeat[((size_t)l * P + p) * 2]; df[2 * l + 1] = dfeat[((size_t)l * P + p) * 2 + 1]; }
       ngp_scatter(lv, gtable, x01, inside, df);
     }

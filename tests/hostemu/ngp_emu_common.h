@@ -8,6 +8,7 @@
 #include <vector>
 struct float2 { float x, y; };                     // ngp_device.h names it in a field helper
 #include "../../sparsefusion_amd/csrc/ngp_device.h"
+#include "../../sparsefusion_amd/csrc/ngp_point_attrs.h"       // ngp_sample_x01
 
 static void fill_levels(NgpLevels* lv, const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype) {
   for (uint32_t l = 0; l < NGP_MAX_LEVELS; ++l) {
@@ -38,8 +39,7 @@ static uint32_t emu_encode_points(const NgpLevels& lv, const float* table, float
   for (uint32_t p = 0; p < P; ++p) {
     const uint32_t n = p / T2;
     float x[3], x01[3];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    const bool inside = ngp_unit(x, bound, x01);
+    const bool inside = ngp_sample_x01<0>(rays_o, rays_d, n, z_s[p], aabb, bound, 0, 0.0f, x, x01);
     n_out += inside ? 0 : 1;
     ngp_encode(lv, table, x01, inside, feat + (size_t)p * NGP_FEAT);
     if (xyz)

@@ -21,15 +21,17 @@ extern "C" void emu_shade_bwd(const float* dcol, const float* rgb_s, const float
   hipemu::launch(blocks, 256, 0, [&] { k_ngp_shade_bwd(a); });
 }
 
-// the point every backward kernel derives for offset e of a sorted sample: ngp_point, then ngp_offset_point (e = 0: the sample itself)
+// the point every backward kernel derives for offset e of a sorted sample (ngp_sample_x01, ngp_point_attrs.h; e = 0: the sample itself)
+static bool emu_sample_x01(const float* rays_o, const float* rays_d, uint32_t n, float z, const float* aabb, float bound, uint32_t e, float eps,
+                           float x[3], float x01[3]) {
+  return e ? ngp_sample_x01<1>(rays_o, rays_d, n, z, aabb, bound, e, eps, x, x01) : ngp_sample_x01<0>(rays_o, rays_d, n, z, aabb, bound, e, eps, x, x01);
+}
 extern "C" void emu_offset_points(const float* rays_o, const float* rays_d, const float* aabb, const float* z_s, uint32_t N, uint32_t T2,
                                   uint32_t e, float eps, float bound, float* xyz) {
   for (uint32_t p = 0; p < N * T2; ++p) {
-    const uint32_t n = p / T2;
-    float x[3], xe[3];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    if (e) ngp_offset_point(x, (int)e, eps, bound, xe);
-    for (int i = 0; i < 3; ++i) xyz[p * 3 + i] = e ? xe[i] : x[i];
+    float x[3], x01[3];
+    emu_sample_x01(rays_o, rays_d, p / T2, z_s[p], aabb, bound, e, eps, x, x01);
+    for (int i = 0; i < 3; ++i) xyz[p * 3 + i] = x[i];
   }
 }
 
@@ -51,10 +53,8 @@ extern "C" void emu_field_bwd_off(const float* table, const int32_t* h_offsets, 
   acc.convert();
   for (uint32_t p = 0; p < P; ++p) {
     const uint32_t n = p / T2;
-    float x[3], xe[3], x01[3];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    ngp_offset_point(x, (int)e, eps, bound, xe);
-    const bool inside = ngp_unit(xe, bound, x01);
+    float xe[3], x01[3];
+    const bool inside = ngp_sample_x01<1>(rays_o, rays_d, n, z_s[p], aabb, bound, e, eps, xe, x01);
     ngp_encode(lv, table, x01, inside, feat + (size_t)p * NGP_FEAT);
     for (int i = 0; i < 3; ++i) xyz[p * 3 + i] = xe[i];
     inside_out[p] = inside ? 1.0f : 0.0f;
@@ -70,10 +70,8 @@ extern "C" void emu_offset_features(const float* table, const int32_t* h_offsets
   fill_levels(&lv, h_offsets, L, S, H, gridtype);
   for (uint32_t p = 0; p < P; ++p) {
     const uint32_t n = p / T2;
-    float x[3], xe[3], x01[3];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    ngp_offset_point(x, (int)e, eps, bound, xe);
-    const bool inside = ngp_unit(xe, bound, x01);
+    float xe[3], x01[3];
+    const bool inside = ngp_sample_x01<1>(rays_o, rays_d, n, z_s[p], aabb, bound, e, eps, xe, x01);
     ngp_encode(lv, table, x01, inside, feat + (size_t)p * NGP_FEAT);
     for (int i = 0; i < 3; ++i) xyz[p * 3 + i] = xe[i];
     inside_out[p] = inside ? 1.0f : 0.0f;
@@ -83,6 +81,7 @@ extern "C" void emu_offset_features(const float* table, const int32_t* h_offsets
 // The table gradient of ONE level from a level-major d(feat) image at offset e, in double: want[row][ch] = sum w_corner dfeat (the fp32
 // corner weights ngp_cell gives, as the kernels compute them; the products and sums exact to 2^-53), sum_abs the same over magnitudes,
 // count the number of addends per element.  want / sum_abs / count: [hsize][2] of that level.
+// e == 0: the samples themselves, no offset.
 extern "C" void emu_scatter_ref64(const int32_t* h_offsets, uint32_t L, float S, uint32_t H, uint32_t gridtype, float bound,
                                   const float* rays_o, const float* rays_d, const float* aabb, const float* z_s, const float* dfeat, uint32_t P,
                                   uint32_t T2, uint32_t level, uint32_t e, float eps, double* want, double* sum_abs, double* count) {
@@ -90,10 +89,8 @@ extern "C" void emu_scatter_ref64(const int32_t* h_offsets, uint32_t L, float S,
   fill_levels(&lv, h_offsets, L, S, H, gridtype);
   for (uint32_t p = 0; p < P; ++p) {
     const uint32_t n = p / T2;
-    float x[3], xe[3], x01[3];
-    ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-    ngp_offset_point(x, (int)e, eps, bound, xe);
-    if (!ngp_unit(xe, bound, x01)) continue;
+    float x[3], x01[3];
+    if (!emu_sample_x01(rays_o, rays_d, n, z_s[p], aabb, bound, e, eps, x, x01)) continue;
     NgpCell c;
     ngp_cell(lv, level, x01, c);
     for (int ch = 0; ch < 2; ++ch) {
@@ -119,10 +116,8 @@ extern "C" int emu_bin_scatter_off(const int32_t* h_offsets, uint32_t L, float S
   if (use_ref) {
     for (uint32_t p = 0; p < P; ++p) {
       const uint32_t n = p / T2;
-      float x[3], xe[3], x01[3], df[NGP_FEAT] = {0};
-      ngp_point(rays_o + n * 3, rays_d + n * 3, z_s[p], aabb, x);
-      ngp_offset_point(x, (int)e, eps, bound, xe);
-      const bool inside = ngp_unit(xe, bound, x01);
+      float xe[3], x01[3], df[NGP_FEAT] = {0};
+      const bool inside = ngp_sample_x01<1>(rays_o, rays_d, n, z_s[p], aabb, bound, e, eps, xe, x01);
       for (uint32_t l = first_level; l < L; ++l) { df[2 * l] = dfeat[((size_t)l * P + p) * 2]; df[2 * l + 1] = dfeat[((size_t)l * P + p) * 2 + 1]; }
       ngp_scatter(lv, gtable, x01, inside, df);
     }

@@ -255,13 +255,17 @@ def scatter_ref64(params, o, d, aabb, z_s, dfeat, level, e, eps=EPS, gridtype=1)
     return want, sum_abs, count
 
 
-def scatter_bound(want, sum_abs, count, merged):
+def scatter_bound(want, sum_abs, count, merged, fp32_addends=False):
     """Per element: every contribution w df is one fp32 product (u), on a z-dropped level behind one fp32 sum of two corner weights (u), and
     in a pair entry of the binned scatter the smaller corner's is rebuilt as a * (wl / wh): two more roundings (2 u) -- 4 u sum|terms|.
     `merged` (the levels of k_ngp_scatter): equal rows of up to 32 consecutive samples of a ray are first summed in an fp32 register, a chain
-    of at most 32 additions: + 32 u sum|terms|.  Each addend is rounded once to 2^-44 fixed point (2^-45 each); one conversion to fp32."""
+    of at most 32 additions: + 32 u sum|terms|.  Each addend is rounded once to 2^-44 fixed point (2^-45 each); one conversion to fp32.
+    `fp32_addends` (a threshold low enough that addends take sf_grad_add's fp32 atomic): the chain term of tests/ngp_bwd_cases.py -- k
+    addends in any order cost k u sum|addend|, with k <= count and the sum <= sum|terms| -- and the final rounding is 3 u |want|."""
     b = (4.0 + (32.0 if merged else 0.0)) * U24 * sum_abs + count * 2.0 ** -45 + TINY
-    return b + U24 * (want.abs() + b)
+    if fp32_addends:
+        b = b + count * U24 * sum_abs
+    return b + (3.0 if fp32_addends else 1.0) * U24 * (want.abs() + b)
 
 
 # ------------------------------------------------------------------------------------------------------------------- descent

@@ -2,7 +2,9 @@
 k_ngp_field_bwd_mfma), against the references and derived bounds of tests/ngp_bwd_cases.py.  The C ABI is driven directly -- forward with a
 field cache, then the backward -- so that T is free; d(sigma), d(rgb) and d(feat) are read from the workspace ([0, M), [M, 4M) and [4M, 36M)
 level-major, M = 2 N T).  Stage B is checked on the d(sigma) / d(rgb) the GPU's own stage A produced, so each stage stands alone.  The table
-gradient stays with tests/test_gpu_ngp.py, which rests on the d(feat) checked here.  Margins: profiles/ngp_bwd_parity_margins.log."""
+gradient of pass 0 is checked per element on small shapes at the end of this file, one level of each scatter kernel (csrc/ngp_scatter.h,
+ngp_scatter_bin.h) on the d(feat) the GPU's own stage B produced; the renders of tests/test_gpu_ngp.py hold it to a norm.
+Margins: profiles/ngp_bwd_parity_margins.log."""
 import ctypes as C
 import functools
 
@@ -10,7 +12,8 @@ import pytest
 import torch
 
 import ngp_bwd_cases as nb
-from ngp_common import params_from_cfg
+import shaded_bwd_common as sb
+from ngp_common import log2_scale, params_from_cfg
 from oracle import ngp_ref
 
 pytestmark = pytest.mark.gpu
@@ -61,8 +64,9 @@ def _forward(net, p, o, d, T, uc, uf):
                 W=[t.cpu() for t in params[1:]])
 
 
-def _backward(fwd, gi, gw, use_cache=True, sigma=None):
-    """sf_ngp_render_backward on a forward's sorted ray -> the six MLP gradients, d(sigma) [N, 2T], d(rgb) [N, 2T, 3], d(feat) [M, 32] (CPU)."""
+def _backward(fwd, gi, gw, use_cache=True, sigma=None, rays_per_row=0):
+    """sf_ngp_render_backward on a forward's sorted ray -> the six MLP gradients, the table gradient, d(sigma) [N, 2T], d(rgb) [N, 2T, 3],
+    d(feat) [M, 32] (CPU)."""
     from sparsefusion_amd import _lib
     N, T = fwd["N"], fwd["T"]
     M = N * 2 * T
@@ -77,10 +81,10 @@ def _backward(fwd, gi, gw, use_cache=True, sigma=None):
     gid, gwd = gi.to(DEV).contiguous(), gw.to(DEV).contiguous()
     _lib.check(lib.sf_ngp_render_backward(C.byref(f), C.byref(gs), _lib.ptr(fwd["o"]), _lib.ptr(fwd["d"]), _lib.ptr(fwd["aabb"]), N, T,
                                           _lib.ptr(fwd["nears"]), _lib.ptr(fwd["fars"]), _lib.ptr(fwd["z_s"]), _lib.ptr(sig), _lib.ptr(fwd["rgb_s"]),
-                                          0.0, _lib.ptr(gid), _lib.ptr(gwd), 0, _lib.ptr(fwd["cache"]) if use_cache else None, _lib.ptr(work), wb,
+                                          0.0, _lib.ptr(gid), _lib.ptr(gwd), rays_per_row, _lib.ptr(fwd["cache"]) if use_cache else None, _lib.ptr(work), wb,
                                           _lib.stream_ptr()))
     torch.cuda.synchronize()
-    return dict(grads=[t.cpu() for t in grads[1:]], dsig=work[:M].view(N, 2 * T).cpu(), drgb=work[M:4 * M].view(N, 2 * T, 3).cpu(),
+    return dict(grads=[t.cpu() for t in grads[1:]], table=grads[0].cpu(), dsig=work[:M].view(N, 2 * T).cpu(), drgb=work[M:4 * M].view(N, 2 * T, 3).cpu(),
                 dfeat=work[4 * M:36 * M].view(16, M, 2).permute(1, 0, 2).reshape(M, 32).cpu(), sigma=sig.cpu())
 
 
@@ -199,3 +203,101 @@ def test_opaque_samples(golden_dir):
     semi, sat, tight = nb.opaque_conditions(r["a"])
     print(f"opaque conditions: e in [1e-6, 1e-2] {semi:.3f} one == 1e-15f {sat:.3f} bound <= 1e-4 of the ray's largest |want| {tight:.4f}")
     assert semi >= 0.05 and sat >= 0.05 and tight >= 0.9, (semi, sat, tight)
+
+
+# ------------------------------------------------------------------------------------------- the table gradient of pass 0, per element
+def _table_levels(name, fwd, bwd, o, d, aabb, offs, levels, gridtype, binned, e=0):
+    """The table gradient of a backward on chosen levels against the float64 corner sums of ITS OWN d(feat) (read from the workspace), under
+    scatter_bound: every element of the level, and the level's d(feat) not all zero.  levels: (level, merged) -- merged = k_ngp_scatter,
+    which ngp_scatter_plan itself (csrc/ngp_bwd_plan.h through the harness of tests/test_hostemu_ngp_bwd.py) must give levels [0, last);
+    binned: whether the plan sends the other levels to the binned scatter (else k_ngp_scatter_fine)."""
+    import test_hostemu_ngp_bwd as hb
+    offs = offs.to(torch.int32).cpu()
+    sp = hb._c_scatter_plan(hb._lib(), offs, 16, log2_scale(), 1, fwd["N"], fwd["T"])
+    assert sp["binned"] == binned and all(merged == (level < sp["last"]) for level, merged in levels), (name, sp, levels)
+    for level, merged in levels:
+        assert float(bwd["dfeat"][:, 2 * level:2 * level + 2].abs().max()) > 0, (name, level)
+        want, sum_abs, count = sb.scatter_ref64({"encoder.offsets": offs}, o, d, aabb, fwd["z_s"].cpu(), bwd["dfeat"], level, e, gridtype=gridtype)
+        nb.check_elements(f"{name} table level {level}", bwd["table"][int(offs[level]):int(offs[level + 1])], want,
+                          sb.scatter_bound(want, sum_abs, count, merged))
+
+
+def _large_table_net(p, gridtype):
+    """the teacher's MLP behind a 2^20-row encoder with a random table (the field of tests/test_gpu_ngp.py::
+    test_table_gradient_of_a_large_hash_map_keeps_the_atomic_scatter, or its `tiled` twin): outside the binned scatter"""
+    from sparsefusion_amd.gridencoder import GridEncoder
+    from sparsefusion_amd.nerf import NeRFNetwork, get_default_torch_ngp_opt
+    net = NeRFNetwork(get_default_torch_ngp_opt())
+    net.load_state_dict({k: p[k] for k in net.state_dict().keys()})
+    net = net.to(DEV)
+    enc = GridEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=20, desired_resolution=2048 * net.bound,
+                      gridtype=gridtype, align_corners=False).to(DEV)
+    gen = torch.Generator().manual_seed(31)
+    with torch.no_grad():
+        enc.embeddings.copy_((torch.rand(enc.embeddings.shape, generator=gen) - 0.5).to(DEV))
+    net.encoder, net._handle = enc, None
+    offs = enc.offsets.to(torch.int32).cpu()
+    assert int((offs[1:] - offs[:-1]).max()) > 1 << 19           # ngp_scatter_plan does not bin: a level beyond SB_MAX_BUCKETS buckets
+    return net, offs
+
+
+def _small_rays(n_side, N, T, seed):
+    o, d = ngp_ref.circle_rays(n_side, view=2)
+    o, d = o[:N].contiguous(), d[:N].contiguous()
+    gen = torch.Generator().manual_seed(seed)
+    return o, d, torch.rand(N, T, generator=gen), torch.rand(N, T, generator=gen)
+
+
+@pytest.mark.parametrize("n_side,N,T,rays_per_row", [(7, 37, 11, 0), (16, 128, 20, 16)], ids=["37x11", "128x20_patches"])
+def test_table_gradient_per_element_teacher(golden_dir, n_side, N, T, rays_per_row):
+    """Pass 0 on the teacher field: level 0 through k_ngp_scatter (register-merged runs, the LDS cache; two 8 x 8 patches with the image
+    layout) and level 8 through the binned scatter."""
+    g, p, net = _golden(golden_dir)
+    o, d, uc, uf = _small_rays(n_side, N, T, 40 + N)
+    fwd = _forward(net, p, o, d, T, uc, uf)
+    gi, gw = _upstream(N, 4)
+    bwd = _backward(fwd, gi, gw, rays_per_row=rays_per_row)
+    _table_levels(f"teacher {N}x{T}", fwd, bwd, o, d, p["aabb_train"], p["encoder.offsets"], ((0, True), (8, False)), gridtype=1, binned=True)
+
+
+def test_table_gradient_per_element_large_hash_map(golden_dir):
+    """Pass 0 on the 2^20-row `hash` field, 37 x 11: level 2 through k_ngp_scatter<1024, 0>, level 13 through k_ngp_scatter_fine<0>."""
+    g, p, _ = _golden(golden_dir)
+    net, offs = _large_table_net(p, 'hash')
+    o, d, uc, uf = _small_rays(7, 37, 11, 51)
+    fwd = _forward(net, p, o, d, 11, uc, uf)
+    gi, gw = _upstream(37, 5)
+    bwd = _backward(fwd, gi, gw)
+    _table_levels("large hash 37x11", fwd, bwd, o, d, p["aabb_train"], offs, ((2, True), (13, False)), gridtype=0, binned=False)
+
+
+def test_table_gradient_per_element_large_tiled_map(golden_dir):
+    """The 2^20-row `tiled` field, 37 x 11, random sorted depths in place of the forward's (some samples leave the box; the backward
+    re-gathers): levels 10 .. 15 are z-dropped and, the table being outside the bins, go through k_ngp_scatter_fine -- level 12 there and
+    level 2 through k_ngp_scatter for pass 0, and level 12 of one offset pass (e = 3) for k_ngp_scatter_fine<1>."""
+    from sparsefusion_amd import _lib
+    g, p, _ = _golden(golden_dir)
+    net, offs = _large_table_net(p, 'tiled')
+    N, T, e = 37, 11, 3
+    o, d, uc, uf = _small_rays(7, N, T, 52)
+    fwd = _forward(net, p, o, d, T, uc, uf)
+    gen = torch.Generator().manual_seed(53)
+    fwd["z_s"] = (torch.rand(N, 2 * T, generator=gen) * 9.0 + 1.0).sort(1).values.contiguous().to(DEV)
+    gi, gw = _upstream(N, 6)
+    bwd = _backward(fwd, gi, gw, use_cache=False)
+    _table_levels("large tiled 37x11", fwd, bwd, o, d, p["aabb_train"], offs, ((2, True), (12, False)), gridtype=1, binned=False)
+    # one offset pass on the same field and depths
+    M = N * 2 * T
+    grads = [torch.zeros_like(t) for t in fwd["params"]]
+    gs = _lib.SfNgpFieldGrad()
+    (gs.g_embeddings, gs.g_w0, gs.g_b0, gs.g_w1, gs.g_b1, gs.g_w2, gs.g_b2) = (t.data_ptr() for t in grads)
+    f = fwd["handle"].struct(fwd["params"])
+    lib = _lib.lib()
+    wb = lib.sf_ngp_render_workspace_bytes(N, T)
+    work = torch.zeros(wb // 4, device=DEV)
+    ds_e = torch.randn(N, 2 * T, generator=gen).to(DEV)
+    _lib.check(lib.sf_ngp_render_offset_backward(C.byref(f), C.byref(gs), _lib.ptr(fwd["o"]), _lib.ptr(fwd["d"]), _lib.ptr(fwd["aabb"]), N, T,
+                                                 _lib.ptr(fwd["z_s"]), _lib.ptr(ds_e), e, sb.EPS, 0, _lib.ptr(work), wb, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    off = dict(table=grads[0].cpu(), dfeat=work[4 * M:36 * M].view(16, M, 2).permute(1, 0, 2).reshape(M, 32).cpu())
+    _table_levels(f"large tiled 37x11 e={e}", fwd, off, o, d, p["aabb_train"], offs, ((12, False),), gridtype=1, binned=False, e=e)

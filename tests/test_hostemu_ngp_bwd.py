@@ -21,7 +21,7 @@ pytestmark = pytest.mark.skipif(not fused.available(), reason="host clang not fo
 def _lib():
     srcs = [os.path.join(HERE, "ngp_bwd_emu.cpp"), os.path.join(HERE, "hip_emu.h"), os.path.join(HERE, "ngp_emu_common.h")] + \
            [os.path.join(HERE, "..", "..", "sparsefusion_amd", "csrc", f)
-            for f in ("ngp_bwd_mfma.h", "ngp_scatter_bin.h", "ngp_bwd_plan.h", "ngp_device.h", "sf_dev.h", "sf_fix.h")]
+            for f in ("ngp_bwd_mfma.h", "ngp_scatter_bin.h", "ngp_bwd_plan.h", "ngp_point_attrs.h", "ngp_device.h", "sf_dev.h", "sf_fix.h")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(SO), exist_ok=True)
         subprocess.check_call([fused.CLANG, "-std=c++17", "-O2", "-fPIC", "-shared", "-I" + HERE, "-Wall", "-Wno-unused-function",

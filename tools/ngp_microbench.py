@@ -8,7 +8,9 @@ albedo render's forward + backward at the same size, and the composed route -- t
 NeRFNetwork.forward(x, d, l, ratio, 'lambertian') under autograd on the sorted points (seven field evaluations through the grid-encode
 op) and torch compositing.
 --bwd-pipe 0|1 selects the kernel of the cached field backward (renderer._FIELD_BWD_PIPE) instead of the default.
---feat-cache 0|1 sets renderer._FEAT_CACHE: 0 = no field cache, the backward re-gathers the features (k_ngp_field_bwd_mfma)."""
+--feat-cache 0|1 sets renderer._FEAT_CACHE: 0 = no field cache, the backward re-gathers the features (k_ngp_field_bwd_mfma).
+--log2-hashmap N --gridtype hash|tiled swaps the encoder for one of 2^N rows per level (random table): with N = 20 the table is outside the
+binned scatter and the backward takes k_ngp_scatter + k_ngp_scatter_fine (csrc/ngp_scatter.h), which the default teacher field never launches."""
 import os
 import sys
 import time
@@ -32,6 +34,16 @@ p = ngp_ref.init_params(bound=4, seed=1, table_std=0.5, sigma_bias=-3.0)
 net = NeRFNetwork(get_default_torch_ngp_opt())
 net.load_state_dict({k: p[k] for k in net.state_dict().keys()})
 net = net.to(dev).train()
+if "--log2-hashmap" in sys.argv:
+    from sparsefusion_amd.gridencoder import GridEncoder
+    log2_rows = int(sys.argv[sys.argv.index("--log2-hashmap") + 1])
+    gridtype = sys.argv[sys.argv.index("--gridtype") + 1] if "--gridtype" in sys.argv else "hash"
+    enc = GridEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=log2_rows,
+                      desired_resolution=2048 * net.bound, gridtype=gridtype, align_corners=False).to(dev)
+    with torch.no_grad():
+        enc.embeddings.copy_((torch.rand(enc.embeddings.shape, generator=torch.Generator().manual_seed(1)) - 0.5).to(dev))
+    net.encoder, net._handle = enc, None
+    print(f"encoder         : {gridtype}, 2^{log2_rows} rows per level")
 o, d = ngp_ref.circle_rays(128, view=7)
 o, d = o[None].to(dev), d[None].to(dev)
 kw = dict(staged=False, perturb=True, bg_color=0, shading='albedo', **vars(net.opt))
